@@ -18,13 +18,18 @@ timed region besides the barriers; time = max over ranks. Two ways in:
 `--backend nccl` (default: RCCL, rank r on GPU r) or `gloo` (ranks may share a GPU: rank r on GPU
 r mod the device count — how the N>1 path is exercised on a one-GPU box).
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus `roofline` (dominant kernel:
+A plain run sets up, warms up, times `--steps` steps and prints ONE JSON line (rank 0) with the
+contract fields (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...)
+and the step roofline computed from `ms_per_step` alone. `--dump-outputs DIR` also writes what the
+last timed step returned (`ids.npy`, `mel.npy`; float32). Everything else the benchmark measures
+needs runs of its own and sits behind `--full`: `roofline` (dominant kernel:
 the kernel symbol with the most device time per step, grouped as rocprofv3 --stats groups them, from
 begin/end timestamps of every launch in a serialised profiling pass; at C2 that is the decode's
 encoder-space cross-attention, whose per-launch time is then taken from device stamps in its
-decode-graph nodes in a pass pipelined exactly as the timed region) and
-`cpu_baseline` (the fp32 PyTorch-CPU restatement, both reference decode modes, timed on this host,
-rank 0 / N=1 only).
+decode-graph nodes in a pass pipelined exactly as the timed region), `phases`, `biased_wer` (the
+boosted decode scored against the lam = 0 decode) and `cpu_baseline` (the fp32 PyTorch-CPU
+restatement, both reference decode modes, timed on this host, rank 0 / N=1 only). Under `--full`,
+`--no-profile` and `--no-cpu-baseline` leave out the profiling passes / the CPU leg.
 
 `--reference-mode`: the reference's own decode contract instead of the benchmark mode —
 natural EOS, max_length=225, no boost (scripts/evaluation.py:173-179), same clips; its line goes to
@@ -294,6 +299,24 @@ def launch_ranks(cmd, n, env_extra=None, grace_s=15.0, poll_s=0.2):
     return (rc if rc >= 0 else 128 - rc), last_json[0]
 
 
+DUMP_MAX_BYTES = 64 * 1000 * 1000   # all files of one --dump-outputs together
+
+
+def dump_outputs(outdir: str, tensors: dict, max_bytes: int = DUMP_MAX_BYTES):
+    """--dump-outputs: the arrays the last timed step returned, as outdir/<name>.npy in float32 (token ids
+    are below 2^24: exact). An array over its share of `max_bytes` is written as a fixed sample: the
+    elements at sorted flat indices drawn once from numpy.random.default_rng(0), the same for every
+    run of the same shapes, so two builds are compared element for element."""
+    os.makedirs(outdir, exist_ok=True)
+    share = max_bytes // max(len(tensors), 1) // 4   # elements per array
+    for name, t in tensors.items():
+        a = t.detach().to("cpu").float().numpy()
+        if a.size > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=share, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -311,8 +334,13 @@ def main():
     ap.add_argument("--boost", type=float, default=2.0)
     ap.add_argument("--dtype", default="bf16")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the profiling passes (roofline, phases), the biased-WER "
+                         "scoring and the CPU baseline (a plain run times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32): ids, mel")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: skip the profiling passes")
     ap.add_argument("--profile-steps", type=int, default=2, help="steps of the serialised roofline pass")
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE",
                     help="wcb_set_option on the handle (alternative formulations, for sweeps)")
@@ -327,6 +355,10 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        args.no_profile = args.no_cpu_baseline = True
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # launcher: N fresh rank processes of this script, started before anything here touches the GPU
         rc, _ = launch_ranks([sys.executable, "-u", os.path.abspath(__file__)] + sys.argv[1:], args.gpus)
@@ -417,7 +449,8 @@ def main():
         model.synchronize()
         torch.cuda.synchronize()
         log(f"warmup {i} done, ids {tuple(ids.shape)}")
-    assert ids.shape[0] == B and (args.num_beams > 1 or min_new == 0 or ids.shape == (B, args.new_tokens))
+    if args.warmup:
+        assert ids.shape[0] == B and (args.num_beams > 1 or min_new == 0 or ids.shape == (B, args.new_tokens))
     keep.clear()
     if world > 1:
         dist.barrier()
@@ -435,6 +468,8 @@ def main():
     elapsed = max_over_ranks(time.perf_counter() - t0, dev)
     ms_per_step = elapsed / args.steps * 1e3
     value = world * B * 30.0 / (elapsed / args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"mel": keep[-1][0], "ids": keep[-1][1]})
     keep.clear()
 
     # ---- per-kernel-class roofline: a separate, untimed pass of the same step in which every launch
@@ -558,7 +593,7 @@ def main():
     # token ids as words — WER, compute_bias_wer's tallies over the bias list, and the recall of the
     # placed phrases (each clip's runner-up continuation, absent from its lam = 0 decode); untimed
     bias_plumb = None
-    if rank == 0 and args.boost > 0:
+    if rank == 0 and args.boost > 0 and args.full:
         import ctypes as C
         from whisper_context_biasing_amd import _lib
         from whisper_context_biasing_amd.metrics import _cstrs, wer_counts

@@ -9,7 +9,7 @@ if [ -n "${TESTS:-}" ]; then
   timeout -k 10 900 python -u -m pytest -x -q --timeout 300 --timeout-method thread $TESTS ${K:+-k "$K"} > "$O/tests.log" 2>&1 || { tail -30 "$O/tests.log"; exit 1; }
   tail -3 "$O/tests.log"
 fi
-timeout -k 10 400 python bench.py --no-cpu-baseline ${BENCH_ARGS:-} > "$O/bench_default.json" 2> "$O/bench_default.err" || { tail -20 "$O/bench_default.err"; exit 1; }
+timeout -k 10 400 python bench.py --full --no-cpu-baseline ${BENCH_ARGS:-} > "$O/bench_default.json" 2> "$O/bench_default.err" || { tail -20 "$O/bench_default.err"; exit 1; }
 python -c "import json;d=json.load(open('$O/bench_default.json'));print('default', d['value'], d['ms_per_step'])"
 for o in ${OPT:-}; do   # one run per word; NAME=V,NAME2=V2 sets several options in one run
   a=""; for kv in ${o//,/ }; do a="$a --opt $kv"; done

@@ -7,5 +7,5 @@ timeout -k 10 60 ./tools/cumask_probe > "$O/cumask.txt" 2>&1 || { cat "$O/cumask
 head -5 "$O/cumask.txt"
 timeout -k 10 900 python -u -m pytest tests/test_gpu_stepwise.py tests/test_gpu_shard.py -m gpu -x -v --timeout 600 --timeout-method thread --durations=15 > "$O/pytest.log" 2>&1
 rc=$?; tail -25 "$O/pytest.log"; [ $rc = 0 ] || exit $rc
-timeout -k 10 300 python bench.py --no-cpu-baseline --steps 10 > "$O/c2.json" 2> "$O/c2.err" || { tail -20 "$O/c2.err"; exit 1; }
+timeout -k 10 300 python bench.py --full --no-cpu-baseline --steps 10 > "$O/c2.json" 2> "$O/c2.err" || { tail -20 "$O/c2.err"; exit 1; }
 python -c "import json;d=json.load(open('$O/c2.json'));print('C2',d['value'],d['ms_per_step'],d['roofline']['frac'],d['roofline']['traffic'],d['roofline']['step']['frac'])"

@@ -13,7 +13,7 @@ fi
 for i in $(seq 1 ${REPS:-3}); do
   for v in new old; do
     cp "$O/$v.so" "$L" || exit 1
-    timeout -k 10 300 python bench.py --no-cpu-baseline ${BENCH_ARGS:-} > "$O/b_$v.$i.json" 2> "$O/b.err" || { tail -20 "$O/b.err"; cp "$O/new.so" "$L"; exit 1; }
+    timeout -k 10 300 python bench.py --full --no-cpu-baseline ${BENCH_ARGS:-} > "$O/b_$v.$i.json" 2> "$O/b.err" || { tail -20 "$O/b.err"; cp "$O/new.so" "$L"; exit 1; }
     python -c "
 import json;d=json.load(open('$O/b_$v.$i.json'));ph=d.get('phases') or {}
 print('$v', d['value'], d['ms_per_step'], {k: round(ph[k]['ms_per_step'],3) for k in ${PHASES:-['dec_xmerge','dec_xattn']} if k in ph})"

@@ -6,7 +6,7 @@ R="$GRAFT_REPO_ROOT"; cd "$R" || exit 1
 O="$R/gpurun_out/phases"; mkdir -p "$O"
 for o in default ${OPT:-}; do
   a=""; [ "$o" != default ] && a="--opt $o"
-  timeout -k 10 400 python bench.py --no-cpu-baseline $a ${BENCH_ARGS:-} > "$O/$o.json" 2> "$O/$o.err" || { tail -20 "$O/$o.err"; exit 1; }
+  timeout -k 10 400 python bench.py --full --no-cpu-baseline $a ${BENCH_ARGS:-} > "$O/$o.json" 2> "$O/$o.err" || { tail -20 "$O/$o.err"; exit 1; }
   python - "$O/$o.json" "$o" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

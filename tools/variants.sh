@@ -4,9 +4,10 @@
 set -o pipefail
 cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p gpurun_out
+O="$_"   # the directory made above
 IFS=';' read -ra VS <<< "${VARIANTS:-X=0}"
 for v in "${VS[@]}"; do
-  env $v timeout -k 10 300 python bench.py --steps ${STEPS:-20} --warmup 3 --no-cpu-baseline "$@" > gpurun_out/v.json 2> gpurun_out/v.err || { tail -20 gpurun_out/v.err; exit 1; }
+  env $v timeout -k 10 300 python bench.py --steps ${STEPS:-20} --warmup 3 --full --no-cpu-baseline "$@" > "$O/v.json" 2> "$O/v.err" || { tail -20 "$O/v.err"; exit 1; }
   python - "$v" <<'PY'
 import json, sys
 d = json.load(open("gpurun_out/v.json"))
