@@ -21,6 +21,7 @@ extern "C" {
 
 typedef struct wcb_handle wcb_handle;
 typedef struct wcb_bias wcb_bias;
+typedef struct wcb_bias_batch wcb_bias_batch;
 
 enum wcb_status {
   WCB_OK = 0,
@@ -240,6 +241,39 @@ int wcb_bias_create(wcb_handle* h, const int32_t* tokens, const int32_t* offsets
                     const uint8_t* word_start, wcb_bias** out);
 void wcb_bias_destroy(wcb_bias* b);
 int wcb_bias_num_states(const wcb_bias* b);
+
+/* Per-utterance bias lists: clip b of a batch is boosted with its own phrase list L_b (possibly empty), every
+ * decoder row of clip b (greedy: row b; beams: rows b·nb .. b·nb+nb-1) scored exactly as one wcb_bias of L_b
+ * would score it; the same lambda and word_start mask for every clip.
+ * wcb_bias_batch_create compiles B automata into one forest: phrase p = tokens[phrase_off[p] ..
+ * phrase_off[p+1]), clip b owns phrases clip_off[b] .. clip_off[b+1]) (host arrays; phrase_off has
+ * clip_off[B] + 1 entries). One state space with a root state per clip: trans_off / trans_tok / trans_dst /
+ * st_depth / st_keep are global CSR arrays as in wcb_bias, and each clip's gated root children are a
+ * token-sorted list (rc_off[B+1], rc_tok, rc_dst) — no vocabulary-sized array per clip. The object is HOST
+ * data bound to no stream: a decode call copies it (asynchronously, on the decode stream) into device buffers
+ * the handle owns, so it may be destroyed as soon as that call returns, async_out = 1 included. Token ids
+ * outside [0, vocab), decreasing offsets and B outside 1..64 are WCB_ERR_ARG.
+ * wcb_bias_batch_num_states: the states of clip `clip`'s automaton (root included), clip = -1: of the forest. */
+int wcb_bias_batch_create(wcb_handle* h, int B, const int32_t* tokens, const int32_t* phrase_off,
+                          const int32_t* clip_off, const uint8_t* word_start, wcb_bias_batch** out);
+void wcb_bias_batch_destroy(wcb_bias_batch* bb);
+int wcb_bias_batch_num_states(const wcb_bias_batch* bb, int clip);
+
+/* wcb_generate with the forest in place of the shared automaton (bb built for exactly B clips, else
+ * WCB_ERR_ARG). The device buffers the forest is copied into have a capacity that only grows (a larger forest
+ * waits for the handle's queued work and reallocates); the captured decode graph reads the forest through
+ * them, so successive calls with different lists within the capacity replay the same graph. */
+int wcb_generate_biased(wcb_handle* h, const float* mel, int B, const wcb_gen_cfg* cfg, const wcb_bias_batch* bb,
+                        const int32_t* prefix, int prefix_len, int32_t* out_ids, int32_t* out_steps, void* stream);
+
+/* installs the forest on a step-wise state: after wcb_decode_begin / wcb_decode_begin_beams (bb built for
+ * the state's B clips), before the first wcb_decode_step; every wcb_decode_step of that state must then be
+ * given bias = NULL (a non-NULL bias is WCB_ERR_ARG). */
+int wcb_decode_bias_batch(wcb_handle* h, wcb_state* st, const wcb_bias_batch* bb);
+
+/* debug counters by name (not part of wcb_profile_read): "graph_captures" = decode graphs instantiated so
+ * far on this handle. Unknown name: WCB_ERR_ARG. */
+int wcb_debug_counter(const wcb_handle* h, const char* name, int64_t* out);
 
 /* per-kernel time accounting for the benchmark's roofline. enable bit 0: HIP events around every
  * front-end / encoder launch on its stream; bit 1: device time stamps (s_memrealtime) written by the

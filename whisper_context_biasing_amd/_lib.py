@@ -61,6 +61,13 @@ SIGNATURES = {
     "wcb_bias_create": (C.c_int, [_P, _P, _P, C.c_int, _P, C.POINTER(_P)]),
     "wcb_bias_destroy": (None, [_P]),
     "wcb_bias_num_states": (C.c_int, [_P]),
+    "wcb_bias_batch_create": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.POINTER(_P)]),
+    "wcb_bias_batch_destroy": (None, [_P]),
+    "wcb_bias_batch_num_states": (C.c_int, [_P, C.c_int]),
+    "wcb_generate_biased": (C.c_int, [_P, _P, C.c_int, C.POINTER(WcbGenCfg), _P, _P, C.c_int, _P,
+                                      C.POINTER(C.c_int32), _P]),
+    "wcb_decode_bias_batch": (C.c_int, [_P, _P, _P]),
+    "wcb_debug_counter": (C.c_int, [_P, C.c_char_p, C.POINTER(C.c_int64)]),
     "wcb_debug_copy": (C.c_int, [_P, C.c_char_p, _P, C.c_int64, C.c_int]),
     "wcb_profile_enable": (C.c_int, [_P, C.c_int]),
     "wcb_profile_read": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P]),

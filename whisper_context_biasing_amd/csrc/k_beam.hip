@@ -33,12 +33,26 @@ constexpr float kNeg = -1.0e9f;
 
 WCB_DEV bool beam_better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
 
-// δ(s, tok): trans(s) entry if present, else the root child, else the root (k_select.hip)
-WCB_DEV int ac_delta(const BeamArgs& a, int s, int tok) {
+// δ(s, tok): trans(s) entry if present, else the root child, else the root (k_select.hip). FOREST
+// (per-utterance lists, kernels.h ForestArgs): the root children are the clip's token-sorted list
+// (binary search) and the root is the clip's.
+template <bool FOREST>
+WCB_DEV int ac_delta(const BeamArgs& a, int s, int tok, int clip) {
   for (int t = a.trans_off[s]; t < a.trans_off[s + 1]; ++t)
     if (a.trans_tok[t] == tok) return a.trans_dst[t];
-  const int c = (tok >= 0 && tok < a.V) ? a.root_child[tok] : -1;
-  return c >= 0 ? c : 0;
+  if constexpr (FOREST) {
+    int lo = a.forest.rc_off[clip], hi = a.forest.rc_off[clip + 1];
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      const int v = a.forest.rc_tok[mid];
+      if (v == tok) return a.forest.rc_dst[mid];
+      if (v < tok) lo = mid + 1; else hi = mid;
+    }
+    return a.forest.root[clip];
+  } else {
+    const int c = (tok >= 0 && tok < a.V) ? a.root_child[tok] : -1;
+    return c >= 0 ? c : 0;
+  }
 }
 
 template <int NW>
@@ -86,7 +100,7 @@ __global__ __launch_bounds__(256) void beam_init_kernel(BeamArgs a) {
 // NT threads per row (16 waves when the rows leave CUs idle: one wave per SIMD cannot hide the
 // serial compare-exchange chain of a list insert, which every element of a wave pays when any lane
 // inserts), KL = the per-thread list length (K rounded up: the chain is KL steps long)
-template <int NT, int KL>
+template <int NT, int KL, bool FOREST>
 __global__ __launch_bounds__(NT) void beam_topk_kernel(BeamArgs a) {
   constexpr int NW = NT / 64;
   if (*a.all_done) return;                    // frozen once the search has stopped
@@ -136,11 +150,18 @@ __global__ __launch_bounds__(NT) void beam_topk_kernel(BeamArgs a) {
   int rb = 0, sd = 0, sk = 0;
   if (boost) {
     const int nw = (a.V + 31) >> 5;
-    for (int k = tid; k < nw; k += NT) { bits[k] = a.root_bits[k]; tbits[k] = 0u; }
+    for (int k = tid; k < nw; k += NT) { bits[k] = FOREST ? 0u : a.root_bits[k]; tbits[k] = 0u; }
     __syncthreads();
     for (int t = a.trans_off[st] + tid; t < a.trans_off[st + 1]; t += NT) {
       const int v = a.trans_tok[t];
       atomicOr(&tbits[v >> 5], 1u << (v & 31));
+    }
+    if constexpr (FOREST) {   // the clip's root children (built like tbits; no shared bitmap is read)
+      const int clip = r / a.nb;
+      for (int t = a.forest.rc_off[clip] + tid; t < a.forest.rc_off[clip + 1]; t += NT) {
+        const int v = a.forest.rc_tok[t];
+        atomicOr(&bits[v >> 5], 1u << (v & 31));
+      }
     }
     __syncthreads();
     sd = a.st_depth[st];
@@ -298,7 +319,7 @@ __global__ __launch_bounds__(NT) void beam_chunk_stats_kernel(BeamArgs a) {
   if (tid == 0) *reinterpret_cast<float2*>(a.chunk_stats + ((long)r * a.nchunk + c) * 2) = float2{mc, sc};
 }
 
-template <int NT, int KL>
+template <int NT, int KL, bool FOREST>
 __global__ __launch_bounds__(NT) void beam_topk_chunk_kernel(BeamArgs a) {
   constexpr int NW = NT / 64;
   constexpr int kW = 4 * 1024 / 32;          // bitmap words of a chunk (<= 1024 float4 = 4096 tokens, 32-aligned)
@@ -326,11 +347,18 @@ __global__ __launch_bounds__(NT) void beam_topk_chunk_kernel(BeamArgs a) {
   int rb = 0, sd = 0, sk = 0;
   if (boost) {
     const int nwc = ((v_hi + 31) >> 5) - w_lo;
-    for (int k = tid; k < nwc; k += NT) { bits[k] = a.root_bits[w_lo + k]; tbits[k] = 0u; }
+    for (int k = tid; k < nwc; k += NT) { bits[k] = FOREST ? 0u : a.root_bits[w_lo + k]; tbits[k] = 0u; }
     __syncthreads();
     for (int t = a.trans_off[st] + tid; t < a.trans_off[st + 1]; t += NT) {
       const int v = a.trans_tok[t];
       if (v >= v_lo && v < v_hi) atomicOr(&tbits[(v >> 5) - w_lo], 1u << (v & 31));
+    }
+    if constexpr (FOREST) {   // the clip's root children inside this chunk
+      const int clip = r / a.nb;
+      for (int t = a.forest.rc_off[clip] + tid; t < a.forest.rc_off[clip + 1]; t += NT) {
+        const int v = a.forest.rc_tok[t];
+        if (v >= v_lo && v < v_hi) atomicOr(&bits[(v >> 5) - w_lo], 1u << (v & 31));
+      }
     }
     sd = a.st_depth[st];
     sk = a.st_keep[st];
@@ -422,6 +450,7 @@ __global__ __launch_bounds__(NT) void beam_topk_chunk_kernel(BeamArgs a) {
   }
 }
 
+template <bool FOREST>
 __global__ __launch_bounds__(256) void beam_step_kernel(BeamArgs a) {
   if (*a.all_done) {   // frozen search: a step changes nothing, so every beam extends itself by pad
     if (threadIdx.x < a.nb) {
@@ -549,7 +578,7 @@ __global__ __launch_bounds__(256) void beam_step_kernel(BeamArgs a) {
     a.next_ids[R0 + i] = tt[k];
     if (a.parent) a.parent[R0 + i] = tb[k];
     a.run_sc[R0 + i] = rlp[k];
-    a.state[R0 + i] = a.lam != 0.f ? ac_delta(a, st_old[tb[k]], tt[k]) : 0;
+    a.state[R0 + i] = a.lam != 0.f ? ac_delta<FOREST>(a, st_old[tb[k]], tt[k], b) : (FOREST ? a.forest.root[b] : 0);
     const int m = fsrc[i];
     if (m < nb) {
       a.fin_sc[R0 + i] = fsc_old[m];
@@ -611,7 +640,8 @@ __global__ __launch_bounds__(256) void beam_output_kernel(BeamArgs a) {
 void beam_init(const BeamArgs& a, hipStream_t s) {
   WCB_LAUNCH(beam_init_kernel, dim3(a.B * a.nb), dim3(256), 0, s, a);
 }
-void beam_select(const BeamArgs& a, hipStream_t s) {
+template <bool FOREST>
+static void beam_select_launch(const BeamArgs& a, hipStream_t s) {
   const int rows = a.B * a.nb;
   if (a.nchunk > 1) {   // chunked: (max, Σexp) per chunk, then the chunk top-K lists
     if (a.nchunk > kBeamChunks || a.nb * a.K > 2 * 64 || a.nb * a.nchunk * a.K > 64 * 2 * kBeamChunks)
@@ -621,27 +651,31 @@ void beam_select(const BeamArgs& a, hipStream_t s) {
     WCB_LAUNCH((beam_chunk_stats_kernel<256>), dim3(a.nchunk, rows), dim3(256), 0, s, a);
     auto chunk = [&](auto kl) {
       constexpr int KL = decltype(kl)::value;
-      WCB_LAUNCH((beam_topk_chunk_kernel<256, KL>), dim3(a.nchunk, rows), dim3(256), 0, s, a);
+      WCB_LAUNCH((beam_topk_chunk_kernel<256, KL, FOREST>), dim3(a.nchunk, rows), dim3(256), 0, s, a);
     };
     if (a.K <= 4) chunk(std::integral_constant<int, 4>{});
     else if (a.K <= 8) chunk(std::integral_constant<int, 8>{});
     else if (a.K <= 12) chunk(std::integral_constant<int, 12>{});
     else chunk(std::integral_constant<int, 16>{});
-    WCB_LAUNCH(beam_step_kernel, dim3(a.B), dim3(256), 0, s, a);
+    WCB_LAUNCH((beam_step_kernel<FOREST>), dim3(a.B), dim3(256), 0, s, a);
     return;
   }
   // 16 waves per row while the rows fit one per CU (C5: 80 rows), 8 up to two per CU (C3: 320)
   auto topk = [&](auto kl) {
     constexpr int KL = decltype(kl)::value;
-    if (rows <= 256) WCB_LAUNCH((beam_topk_kernel<1024, KL>), dim3(rows), dim3(1024), 0, s, a);
-    else if (rows <= 1024) WCB_LAUNCH((beam_topk_kernel<512, KL>), dim3(rows), dim3(512), 0, s, a);
-    else WCB_LAUNCH((beam_topk_kernel<256, KL>), dim3(rows), dim3(256), 0, s, a);
+    if (rows <= 256) WCB_LAUNCH((beam_topk_kernel<1024, KL, FOREST>), dim3(rows), dim3(1024), 0, s, a);
+    else if (rows <= 1024) WCB_LAUNCH((beam_topk_kernel<512, KL, FOREST>), dim3(rows), dim3(512), 0, s, a);
+    else WCB_LAUNCH((beam_topk_kernel<256, KL, FOREST>), dim3(rows), dim3(256), 0, s, a);
   };
   if (a.K <= 4) topk(std::integral_constant<int, 4>{});
   else if (a.K <= 8) topk(std::integral_constant<int, 8>{});
   else if (a.K <= 12) topk(std::integral_constant<int, 12>{});
   else topk(std::integral_constant<int, 16>{});
-  WCB_LAUNCH(beam_step_kernel, dim3(a.B), dim3(256), 0, s, a);
+  WCB_LAUNCH((beam_step_kernel<FOREST>), dim3(a.B), dim3(256), 0, s, a);
+}
+void beam_select(const BeamArgs& a, hipStream_t s) {
+  if (a.forest.root) beam_select_launch<true>(a, s);
+  else beam_select_launch<false>(a, s);
 }
 void beam_output(const BeamArgs& a, hipStream_t s) {
   WCB_LAUNCH(beam_output_kernel, dim3(a.B), dim3(256), 0, s, a);

@@ -14,6 +14,13 @@
 // logits once applying lam·(rowbase + root bit), rowbase = k - d of the row's state; the per-row
 // finalize re-scores only trans(s) — exact because lam >= 0 (checked on the host) and n on a trans
 // token is never below the vocabulary-pass value, so an underestimated copy never wins.
+//
+// Per-utterance lists (FOREST, kernels.h ForestArgs): row m scores against its own clip's automaton.
+// The vocabulary pass is handed an all-zero root bitmap, so it applies lam·rowbase only; the finalize
+// re-scores trans(s) and the clip's root-children list (n = k - d + 1). Exact by the same argument: the
+// vocabulary-pass copy of a root child is one lam short (never above its exact value), and a token in
+// both lists keeps the larger candidate, the trans value (never below k - d + 1). delta(s, v) looks in
+// trans(s), then in the clip's list, then falls back to the clip's root.
 #include <algorithm>
 
 #include "common.h"
@@ -62,7 +69,7 @@ __global__ __launch_bounds__(256) void select_partial_kernel(SelectArgs a) {
 // One wave per row; the last row to finish (atomic ticket) advances the step/position counters.
 // EMB: the row's next-step input embedding in the same launch (k_norm.hip embed_kernel's arithmetic and
 // stats grouping, 64 columns per pass).
-template <typename T, bool EMB>
+template <typename T, bool EMB, bool FOREST>
 __global__ __launch_bounds__(64) void select_finalize_kernel(SelectArgs a) {
   const int m = blockIdx.x, lane = threadIdx.x;
   const int step = *a.step;
@@ -87,12 +94,20 @@ __global__ __launch_bounds__(64) void select_finalize_kernel(SelectArgs a) {
       if (mask_eos && v == a.eos) x = -INFINITY;
       if (better(x, v, bv, bi)) { bv = x; bi = v; }
     }
+    if constexpr (FOREST) {   // the clip's root children: n = k - d + 1 (the vocabulary pass gave them k - d)
+      for (int t = a.forest.rc_off[m] + lane; t < a.forest.rc_off[m + 1]; t += 64) {
+        const int v = a.forest.rc_tok[t];
+        float x = bias_bonus(row[v], a.lam, k - d + 1);
+        if (mask_eos && v == a.eos) x = -INFINITY;
+        if (better(x, v, bv, bi)) { bv = x; bi = v; }
+      }
+    }
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     const float ov = __shfl_xor(bv, o, 64);
     const int oi = __shfl_xor(bi, o, 64);
-    if (better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+    if (better(ov, oi, bv, bi)) { bv = ov; bi = oi; }   // (one token from both lists: the larger value stands)
   }
   const bool fin = a.finished[m] != 0;
   // a row with no comparable value (all NaN) keeps bi = INT_MAX: emit EOS rather than an index past
@@ -104,6 +119,13 @@ __global__ __launch_bounds__(64) void select_finalize_kernel(SelectArgs a) {
     if (a.trans_tok[t] == tok) dst = a.trans_dst[t];
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) dst = max(dst, __shfl_xor(dst, o, 64));
+  int rdst = -1;   // FOREST: tok among the clip's root children
+  if constexpr (FOREST) {
+    for (int t = a.forest.rc_off[m] + lane; t < a.forest.rc_off[m + 1]; t += 64)
+      if (a.forest.rc_tok[t] == tok) rdst = a.forest.rc_dst[t];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) rdst = max(rdst, __shfl_xor(rdst, o, 64));
+  }
   if constexpr (EMB) {
     // 8 consecutive columns per lane (16-byte accesses of T; the fragment-major copy holds them
     // contiguously too), the optional per-st_w-column partials in embed_kernel's lane-butterfly order
@@ -146,7 +168,11 @@ __global__ __launch_bounds__(64) void select_finalize_kernel(SelectArgs a) {
     }
   }
   if (lane == 0) {
-    if (dst < 0) dst = (tok >= 0 && tok < a.V && a.root_child[tok] >= 0) ? a.root_child[tok] : 0;
+    if constexpr (FOREST) {
+      if (dst < 0) dst = rdst >= 0 ? rdst : a.forest.root[m];
+    } else {
+      if (dst < 0) dst = (tok >= 0 && tok < a.V && a.root_child[tok] >= 0) ? a.root_child[tok] : 0;
+    }
     a.state[m] = dst;
     a.rowbase[m] = a.st_keep[dst] - a.st_depth[dst];
     a.next_ids[m] = tok;
@@ -217,16 +243,33 @@ void write_i32(int* dst, const int* host_src, int n, hipStream_t s) {
   }
 }
 
-void select_finalize(const SelectArgs& a, hipStream_t s) {
+template <bool FOREST>
+static void select_finalize_launch(const SelectArgs& a, hipStream_t s) {
   if (!a.emb) {
-    WCB_LAUNCH((select_finalize_kernel<float, false>), dim3(a.M), dim3(64), 0, s, a);
+    WCB_LAUNCH((select_finalize_kernel<float, false, FOREST>), dim3(a.M), dim3(64), 0, s, a);
   } else if (a.dtype == kBF16) {
-    WCB_LAUNCH((select_finalize_kernel<bf16_t, true>), dim3(a.M), dim3(64), 0, s, a);
+    WCB_LAUNCH((select_finalize_kernel<bf16_t, true, FOREST>), dim3(a.M), dim3(64), 0, s, a);
   } else if (a.dtype == kF16) {
-    WCB_LAUNCH((select_finalize_kernel<f16_t, true>), dim3(a.M), dim3(64), 0, s, a);
+    WCB_LAUNCH((select_finalize_kernel<f16_t, true, FOREST>), dim3(a.M), dim3(64), 0, s, a);
   } else {
-    WCB_LAUNCH((select_finalize_kernel<float, true>), dim3(a.M), dim3(64), 0, s, a);
+    WCB_LAUNCH((select_finalize_kernel<float, true, FOREST>), dim3(a.M), dim3(64), 0, s, a);
   }
+}
+void select_finalize(const SelectArgs& a, hipStream_t s) {
+  if (a.forest.root) select_finalize_launch<true>(a, s);
+  else select_finalize_launch<false>(a, s);
+}
+
+// decode start with per-utterance lists: every row in its clip's root state (the zero fill means "state 0",
+// which is clip 0's root only)
+__global__ void forest_init_kernel(ForestArgs f, int* state, int* rowbase, int R, int nb) {
+  for (int r = blockIdx.x * blockDim.x + threadIdx.x; r < R; r += gridDim.x * blockDim.x) {
+    state[r] = f.root[r / nb];
+    if (rowbase) rowbase[r] = 0;   // keep - depth of a root
+  }
+}
+void forest_init(const ForestArgs& f, int* state, int* rowbase, int R, int nb, hipStream_t s) {
+  WCB_LAUNCH(forest_init_kernel, dim3((R + 255) / 256), dim3(256), 0, s, f, state, rowbase, R, nb);
 }
 
 void select_greedy(const SelectArgs& a, hipStream_t s) {

@@ -228,6 +228,18 @@ void logmel_normalize(float* mel, const unsigned* clip_max, int B, int n_mel, hi
 void mel_to_conv_input(DType t, const float* mel, int B, int n_mel, void* xt, long clip_stride,
                        hipStream_t s);
 
+// Per-utterance bias lists: a forest of Aho-Corasick automata in ONE state space (trans_* / st_* of the
+// selection arguments stay global CSR arrays), a root state per clip, and each clip's gated root children
+// as a token-sorted list (no vocabulary-sized array per clip). Decoder row r belongs to clip r / nb.
+struct ForestArgs {
+  const int* root = nullptr;      // [B] root state of clip b
+  const int* rc_off = nullptr;    // [B + 1] clip b's root children: entries rc_off[b] .. rc_off[b + 1]
+  const int* rc_tok = nullptr;    // token ids, ascending within a clip
+  const int* rc_dst = nullptr;    // the depth-1 state each one leads to
+};
+// state[r] = root[r / nb], rowbase[r] = 0 (rowbase nullable) for the R decoder rows of a decode start
+void forest_init(const ForestArgs& f, int* state, int* rowbase, int R, int nb, hipStream_t s);
+
 // greedy selection with bias-list boost (see csrc/k_select.hip for the semantics)
 struct SelectArgs {
   const float* logits = nullptr; long ld = 0; int M = 0; int V = 0;
@@ -252,6 +264,8 @@ struct SelectArgs {
   const void* emb = nullptr; const void* pemb = nullptr; int n_pos = 0, d = 0, dtype = 0;
   float* x = nullptr; void* x16 = nullptr; void* x16fm = nullptr; int fm_nw = 0, fm_kpw = 0;
   float* st = nullptr; int st_w = 16;
+  // per-utterance lists (forest.root non-null): row m is clip m; root_bits must then be all zero
+  ForestArgs forest;
 };
 void select_greedy(const SelectArgs& a, hipStream_t s);          // vocabulary pass + finalize
 void select_finalize(const SelectArgs& a, hipStream_t s);        // partials already written (fused LM head)
@@ -284,6 +298,7 @@ struct BeamArgs {
   int* flags = nullptr;                                 // [B][2]: heuristic unsatisfied, all K hit
   int* out_ids = nullptr; int out_ld = 0; int* out_len = nullptr;
   int* parent = nullptr;                                // [R] (nullable): the beam each running beam extends
+  ForestArgs forest;                                    // per-utterance lists (forest.root non-null): clip = row / nb
 };
 void beam_init(const BeamArgs& a, hipStream_t s);
 void beam_select(const BeamArgs& a, hipStream_t s);   // per-row top-K + per-utterance step

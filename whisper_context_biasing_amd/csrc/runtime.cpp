@@ -119,6 +119,23 @@ struct wcb_bias {
   DevBuf st_depth, st_keep;         // per state: trie depth, deepest completed phrase on its path
 };
 
+// Per-utterance bias lists (wcb.h wcb_bias_batch): B automata compiled on the host into one state space.
+// Host data only; a decode call copies it into the decode context's device buffers (install_forest).
+struct wcb_bias_batch {
+  int B = 0, vocab = 0;
+  std::vector<int> root;                           // [B] root state of clip b (= first state of its block)
+  std::vector<int> n_states;                       // [B] states of clip b's automaton (root included)
+  std::vector<int> rc_off, rc_tok, rc_dst;         // [B + 1], gated root children per clip, token-sorted
+  std::vector<int> trans_off, trans_tok, trans_dst;   // global CSR over all states
+  std::vector<int> st_depth, st_keep;              // per state
+};
+
+// device view of an installed forest (stable pointers into DecCtx::forest)
+struct ForestDev {
+  ForestArgs f;
+  const int *trans_off = nullptr, *trans_tok = nullptr, *trans_dst = nullptr, *st_depth = nullptr, *st_keep = nullptr;
+};
+
 // lean decode projection classes stamped inside the replayed decode graph (stamps pass), by region
 static const char* const kLeanStampClass[] = {"dec_xattn", "dec_qkv", "dec_out", "dec_xq", "dec_xo", "dec_fc1", "dec_fc2",
                                               "dec_kq"};
@@ -146,6 +163,15 @@ struct DecCtx {
   int* done_h = nullptr;                        // pinned: the "all rows finished" step of the last 2 chunks
   hipEvent_t ev_poll[2] = {};
   std::string gkey;
+  // per-utterance bias forest of the call decoding in this context: device buffer carved by the capacities
+  // (states, transitions, root children; they only grow: quiesce + realloc, the graph key names them), the
+  // pinned staging copy the asynchronous upload reads, and the event of the last upload from it
+  DevBuf forest;
+  int f_ns = 0, f_nt = 0, f_nrc = 0;
+  int* f_stage = nullptr;
+  size_t f_stage_words = 0;
+  hipEvent_t ev_fcopy = nullptr;
+  bool f_copy_pending = false;
 };
 
 struct wcb_handle {
@@ -290,6 +316,7 @@ struct wcb_handle {
   // lean path: the residual writers (embedding, out / xo / fc2 projections) also write the 16-bit rows
   // fragment-major for the LayerNorm-fused consumers (QKV, xq, fc1); option "lean_x"
   int lean_x = 1;
+  int64_t n_graph_captures = 0;   // decode graphs instantiated so far (wcb_debug_counter "graph_captures")
   struct wcb_state* step_state = nullptr;   // the active step-wise decode (wcb_decode_begin), if any
   // encoder GEMM tile order (option "enc_raster"): bands of n row panels with the column tiles outer
   // (GemmArgs::raster; 0 = row-major). 8 measured best with the round-3 ring kernel (whisper-small:
@@ -621,6 +648,9 @@ void wcb_destroy(wcb_handle* h) {
     for (hipEvent_t e : D.ev_poll)
       if (e) (void)hipEventDestroy(e);
     if (D.done_h) (void)hipHostFree(D.done_h);
+    D.forest.release();
+    if (D.f_stage) (void)hipHostFree(D.f_stage);
+    if (D.ev_fcopy) (void)hipEventDestroy(D.ev_fcopy);
     for (int i = 0; i < DecCtx::kMaxSub; ++i) {
       if (D.ev_join[i]) (void)hipEventDestroy(D.ev_join[i]);
       if (D.sub[i]) (void)hipStreamDestroy(D.sub[i]);
@@ -1269,6 +1299,7 @@ struct StepCfg {
   // greedy: the step's input embedding was written by the previous step's select_finalize (or by
   // step_embed before the first step), and this step's finalize writes the next one
   bool embedded = false;
+  const ForestDev* forest = nullptr;   // per-utterance bias lists (bias = the empty automaton then: zero root bitmap)
 };
 
 // the residual's fragment-major copy applies (lean path): the lean LayerNorm table covers d, every
@@ -1604,6 +1635,10 @@ void decode_step(wcb_handle* h, const StepCfg& c) {
     s.trans_off = c.bias->trans_off.as<int>(); s.trans_tok = c.bias->trans_tok.as<int>();
     s.trans_dst = c.bias->trans_dst.as<int>(); s.root_child = c.bias->root_child.as<int>();
     s.st_depth = c.bias->st_depth.as<int>(); s.st_keep = c.bias->st_keep.as<int>();
+    if (c.forest) {   // per-utterance lists: the forest's state space, the clip's root children per row
+      s.trans_off = c.forest->trans_off; s.trans_tok = c.forest->trans_tok; s.trans_dst = c.forest->trans_dst;
+      s.st_depth = c.forest->st_depth; s.st_keep = c.forest->st_keep; s.forest = c.forest->f;
+    }
     s.state = next_ids + B; s.finished = next_ids + 2 * B; s.rowbase = next_ids + 3 * B;
     s.eos = h->d.eos_token_id; s.pad = h->d.pad_token_id; s.min_new = c.min_new;
     s.step = ints + I_STEP; s.pos = pos; s.next_ids = next_ids;
@@ -1676,6 +1711,80 @@ void beam_set_bias(BeamArgs& bm, const wcb_bias* bs) {
   bm.trans_off = bs->trans_off.as<int>(); bm.trans_tok = bs->trans_tok.as<int>(); bm.trans_dst = bs->trans_dst.as<int>();
   bm.st_depth = bs->st_depth.as<int>(); bm.st_keep = bs->st_keep.as<int>();
 }
+void beam_set_forest(BeamArgs& bm, const ForestDev& F) {
+  bm.trans_off = F.trans_off; bm.trans_tok = F.trans_tok; bm.trans_dst = F.trans_dst;
+  bm.st_depth = F.st_depth; bm.st_keep = F.st_keep; bm.forest = F.f;
+}
+
+// Per-utterance bias forest of a decode in context D: the host forest copied into the context's device
+// buffer on its decode stream (after the previous decode of the context in stream order, so a replayed
+// graph never sees a half-written forest), through a pinned staging copy the handle owns — the caller may
+// destroy `bb` as soon as the call returns. Device layout (ints), fixed by the capacities so the captured
+// graph's pointers stay valid from call to call:
+//   root [64] | rc_off [128] | st_depth [ns] | st_keep [ns] | trans_off [ns + 64] | trans_tok [nt] |
+//   trans_dst [nt] | rc_tok [nrc] | rc_dst [nrc]
+// A forest above a capacity grows the buffer (quiesce + realloc, as ensure_beam_buf; the graph key names
+// the capacities, so the next call re-captures).
+constexpr int kForestClips = 64;
+int forest_cap(size_t n, int floor_) {
+  size_t c = (size_t)floor_;
+  while (c < n) c *= 2;
+  return (int)c;
+}
+ForestDev install_forest(wcb_handle* h, DecCtx& D, const wcb_bias_batch* bb) {
+  const size_t ns = bb->st_depth.size(), nt = bb->trans_tok.size(), nrc = bb->rc_tok.size();
+  REQUIRE(bb->B <= kForestClips, "bias batch: more than 64 clips");
+  REQUIRE(ns + nt + nrc < ((size_t)1 << 28), "bias batch too large");
+  if ((int)ns > D.f_ns || (int)nt > D.f_nt || (int)nrc > D.f_nrc || !D.forest.p) {
+    const int cs = std::max(D.f_ns, forest_cap(ns, 4096)), ct = std::max(D.f_nt, forest_cap(nt, 4096)),
+              cr = std::max(D.f_nrc, forest_cap(nrc, 1024));
+    quiesce(h);
+    D.forest.release();
+    D.forest.ensure(((size_t)kForestClips + 128 + 3 * (size_t)cs + 64 + 2 * (size_t)ct + 2 * (size_t)cr) * 4);
+    D.f_ns = cs; D.f_nt = ct; D.f_nrc = cr;
+  }
+  int* base = D.forest.as<int>();
+  int* d_root = base;
+  int* d_rcoff = d_root + kForestClips;
+  int* d_depth = d_rcoff + 128;
+  int* d_keep = d_depth + D.f_ns;
+  int* d_toff = d_keep + D.f_ns;
+  int* d_ttok = d_toff + D.f_ns + 64;
+  int* d_tdst = d_ttok + D.f_nt;
+  int* d_rctok = d_tdst + D.f_nt;
+  int* d_rcdst = d_rctok + D.f_nrc;
+  // staging: wait for the upload that last read it, then refill
+  const std::vector<int>* src[9] = {&bb->root, &bb->rc_off, &bb->st_depth, &bb->st_keep, &bb->trans_off,
+                                    &bb->trans_tok, &bb->trans_dst, &bb->rc_tok, &bb->rc_dst};
+  int* dst[9] = {d_root, d_rcoff, d_depth, d_keep, d_toff, d_ttok, d_tdst, d_rctok, d_rcdst};
+  size_t words = 0;
+  for (auto* v : src) words += v->size();
+  if (!D.ev_fcopy) HIPCHK(hipEventCreateWithFlags(&D.ev_fcopy, hipEventDisableTiming));
+  if (D.f_copy_pending) { HIPCHK(hipEventSynchronize(D.ev_fcopy)); D.f_copy_pending = false; }
+  if (words > D.f_stage_words) {
+    if (D.f_stage) (void)hipHostFree(D.f_stage);
+    D.f_stage = nullptr;
+    D.f_stage_words = 0;
+    const size_t cap = std::max<size_t>(words * 2, 1 << 14);
+    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&D.f_stage), cap * 4, hipHostMallocDefault));
+    D.f_stage_words = cap;
+  }
+  size_t o = 0;
+  for (int i = 0; i < 9; ++i) {
+    const size_t n = src[i]->size();
+    if (!n) continue;
+    std::memcpy(D.f_stage + o, src[i]->data(), n * 4);
+    HIPCHK(hipMemcpyAsync(dst[i], D.f_stage + o, n * 4, hipMemcpyHostToDevice, D.hs));
+    o += n;
+  }
+  HIPCHK(hipEventRecord(D.ev_fcopy, D.hs));
+  D.f_copy_pending = true;
+  ForestDev F;
+  F.f.root = d_root; F.f.rc_off = d_rcoff; F.f.rc_tok = d_rctok; F.f.rc_dst = d_rcdst;
+  F.trans_off = d_toff; F.trans_tok = d_ttok; F.trans_dst = d_tdst; F.st_depth = d_depth; F.st_keep = d_keep;
+  return F;
+}
+
 // Lt: the total length cap (prefix + max new tokens, MaxLength), Tc: cache positions, Lg: max new tokens
 BeamArgs beam_args(wcb_handle* h, DecCtx& D, int B, int nb, int P, int Lt, int Tc, int Lg, int min_new, float lam,
                    const wcb_bias* bs) {
@@ -1733,9 +1842,11 @@ int wcb_encode(wcb_handle* h, const float* mel, int B, void* enc_out, void* stre
   });
 }
 
-int wcb_generate(wcb_handle* h, const float* mel, int B, const wcb_gen_cfg* cfg, const wcb_bias* bias,
-                 const int32_t* prefix, int prefix_len, int32_t* out_ids, int32_t* out_steps, void* stream) {
-  return guarded(h, [&] {
+// wcb_generate / wcb_generate_biased: one shared automaton `bias` (or none), or the per-utterance forest `bb`
+static void generate_impl(wcb_handle* h, const float* mel, int B, const wcb_gen_cfg* cfg, const wcb_bias* bias,
+                          const wcb_bias_batch* bb, const int32_t* prefix, int prefix_len, int32_t* out_ids,
+                          int32_t* out_steps, void* stream) {
+  {
     REQUIRE(h && cfg && out_ids && out_steps && B > 0, "bad argument");
     if (!h->ready) throw WcbError(WCB_ERR_STATE, "weights not finalized");
     const int nb = cfg->num_beams;
@@ -1754,6 +1865,10 @@ int wcb_generate(wcb_handle* h, const float* mel, int B, const wcb_gen_cfg* cfg,
     REQUIRE(bs == h->empty_bias.get() || bs->owner == h,
             "bias automaton was created on another handle (wcb_bias_create binds it to its handle)");
     REQUIRE(bs->vocab == h->d.vocab, "bias automaton built for another vocabulary");
+    if (bb) {
+      REQUIRE(bb->vocab == h->d.vocab, "bias batch built for another vocabulary");
+      REQUIRE(bb->B == B, "bias batch: built for " + std::to_string(bb->B) + " clips, the call has " + std::to_string(B));
+    }
     const bool fixed_len = cfg->min_new_tokens >= cfg->max_new_tokens;   // EOS masked: no host polling
     const int out_ld = cfg->max_new_tokens;
     const int Tc = std::min(T, h->d.n_text_ctx);
@@ -1796,8 +1911,15 @@ int wcb_generate(wcb_handle* h, const float* mel, int B, const wcb_gen_cfg* cfg,
       bm = beam_args(h, D, B, nb, P, T, Tc, cfg->max_new_tokens, cfg->min_new_tokens, cfg->bias_boost, bs);
       beam_init(bm, D.hs);   // before the prefill: the self-attention reads keys through bm.phys
     }
+    ForestDev fd;
+    if (bb) {   // per-utterance lists: upload the forest, every row into its clip's root state
+      fd = install_forest(h, D, bb);
+      forest_init(fd.f, ints + I_NEXT + R, nb == 1 ? ints + I_NEXT + 3 * R : nullptr, R, nb, D.hs);
+      if (nb > 1) beam_set_forest(bm, fd);
+    }
     StepCfg sc{R, Tc, out_ld, buf, false, false, D.logits.as<float>(), (long)h->vocab_pad, bs, cfg->bias_boost,
                cfg->min_new_tokens, D.forced.as<int>(), 0};
+    if (bb) sc.forest = &fd;
     sc.clips = B;
     sc.nb = nb;
     sc.xmode = xm;
@@ -1815,8 +1937,12 @@ int wcb_generate(wcb_handle* h, const float* mel, int B, const wcb_gen_cfg* cfg,
       sc.embedded = true;
       step_embed(h, sc);
     }
-    char key[256];
-    snprintf(key, sizeof key, "%d/%d/%d/%d/%llu/%a/%d/%d/%d/%d", B, nb, Tc, out_ld, (unsigned long long)bs->id,
+    // the graph reads a shared automaton through its own buffers (key: its id) and a per-utterance forest
+    // through the context's stable buffers (key: forest mode and the capacities, never the lists)
+    char key[256], bkey[64];
+    if (bb) snprintf(bkey, sizeof bkey, "F%d.%d.%d", D.f_ns, D.f_nt, D.f_nrc);
+    else snprintf(bkey, sizeof bkey, "%llu", (unsigned long long)bs->id);
+    snprintf(key, sizeof key, "%d/%d/%d/%d/%s/%a/%d/%d/%d/%d", B, nb, Tc, out_ld, bkey,
              cfg->bias_boost, cfg->min_new_tokens, h->n_sub, (int)h->prof_stamps, P);
     const int max_new = cfg->max_new_tokens;
     // per-launch HIP events (profiling bit 0) cannot bracket nodes of a replayed graph: eager launches
@@ -1838,6 +1964,7 @@ int wcb_generate(wcb_handle* h, const float* mel, int B, const wcb_gen_cfg* cfg,
         for (int i = 0; i < k; ++i) decode_step(h, sc);
         HIPCHK(hipStreamEndCapture(D.hs, &graph));
         HIPCHK(hipGraphInstantiate(k == 1 ? &D.gexec : &D.gexec_k, graph, nullptr, nullptr, 0));
+        ++h->n_graph_captures;
         HIPCHK(hipGraphDestroy(graph));
       }
       D.gkey = key;
@@ -1916,6 +2043,19 @@ int wcb_generate(wcb_handle* h, const float* mel, int B, const wcb_gen_cfg* cfg,
       if (h->xq_kq) { HIPCHK(hipStreamSynchronize(D.hs)); check_dev_err(h); }
       sync_out(h, stream, D.hs);
     }
+  }
+}
+
+int wcb_generate(wcb_handle* h, const float* mel, int B, const wcb_gen_cfg* cfg, const wcb_bias* bias,
+                 const int32_t* prefix, int prefix_len, int32_t* out_ids, int32_t* out_steps, void* stream) {
+  return guarded(h, [&] { generate_impl(h, mel, B, cfg, bias, nullptr, prefix, prefix_len, out_ids, out_steps, stream); });
+}
+
+int wcb_generate_biased(wcb_handle* h, const float* mel, int B, const wcb_gen_cfg* cfg, const wcb_bias_batch* bb,
+                        const int32_t* prefix, int prefix_len, int32_t* out_ids, int32_t* out_steps, void* stream) {
+  return guarded(h, [&] {
+    REQUIRE(bb, "wcb_generate_biased: the bias batch is required (wcb_generate decodes without one)");
+    generate_impl(h, mel, B, cfg, nullptr, bb, prefix, prefix_len, out_ids, out_steps, stream);
   });
 }
 
@@ -1931,6 +2071,8 @@ struct wcb_state {
   uint64_t bias_id = 0;
   int nb = 1;    // beams per utterance (> 1: beam search, rows R = B·nb; the running beams in bm)
   BeamArgs bm;
+  bool forest = false;   // per-utterance lists installed (wcb_decode_bias_batch): every step takes bias = NULL
+  ForestDev fd;
 };
 
 // step-wise beam search: the beam path of wcb_generate one step per call (begin: cross-K/V of the
@@ -2074,6 +2216,7 @@ int wcb_decode_step(wcb_handle* h, wcb_state* st, const wcb_bias* bias, int32_t*
       }
       REQUIRE(frozen, "max_target_positions reached");
     }
+    REQUIRE(!st->forest || !bias, "wcb_decode_step: the state holds per-utterance lists (wcb_decode_bias_batch): bias must be NULL");
     const wcb_bias* bs = bias ? bias : h->empty_bias.get();
     REQUIRE(bs == h->empty_bias.get() || bs->owner == h, "bias automaton was created on another handle");
     REQUIRE(bs->vocab == h->d.vocab, "bias automaton built for another vocabulary");
@@ -2089,6 +2232,7 @@ int wcb_decode_step(wcb_handle* h, wcb_state* st, const wcb_bias* bias, int32_t*
     sc.host_pos = st->P - 1 + st->steps;
     if (st->nb > 1) {   // beam step: the running beams' new tokens, their scores (running log-prob sums)
       beam_set_bias(st->bm, bs);
+      if (st->forest) beam_set_forest(st->bm, st->fd);
       sc.nb = st->nb;
       sc.phys = st->bm.phys;
       sc.beam = &st->bm;
@@ -2096,6 +2240,7 @@ int wcb_decode_step(wcb_handle* h, wcb_state* st, const wcb_bias* bias, int32_t*
       sc.score_out = scores;
       sc.embedded = true;   // (wcb_decode_begin embedded the first input; each finalize embeds the next)
     }
+    if (st->forest) sc.forest = &st->fd;
     decode_step(h, sc);
     HIPCHK(hipMemcpyAsync(next_ids, D.ints.as<int>() + I_NEXT, (size_t)R * 4, hipMemcpyDeviceToDevice, D.hs));
     if (st->nb > 1 && scores)
@@ -2103,6 +2248,22 @@ int wcb_decode_step(wcb_handle* h, wcb_state* st, const wcb_bias* bias, int32_t*
     st->bias_id = bs->id;
     ++st->steps;
     sync_out(h, stream, D.hs);
+  });
+}
+
+int wcb_decode_bias_batch(wcb_handle* h, wcb_state* st, const wcb_bias_batch* bb) {
+  return guarded(h, [&] {
+    REQUIRE(h && st && st->h == h && h->step_state == st && bb, "bad argument (state of this handle, bias batch)");
+    REQUIRE(st->fwd == 0, "wcb_decode_bias_batch on a forward cache (wcb_forward_cached state)");
+    REQUIRE(st->steps == 0, "wcb_decode_bias_batch: after the first step (install it right after wcb_decode_begin)");
+    REQUIRE(bb->vocab == h->d.vocab, "bias batch built for another vocabulary");
+    REQUIRE(bb->B == st->B, "bias batch: built for " + std::to_string(bb->B) + " clips, the state has " + std::to_string(st->B));
+    DecCtx& D = h->dc[wcb_handle::kMaxCtx - 1];
+    const int R = st->B * st->nb;
+    int* ints = D.ints.as<int>();
+    st->fd = install_forest(h, D, bb);
+    forest_init(st->fd.f, ints + I_NEXT + R, st->nb == 1 ? ints + I_NEXT + 3 * R : nullptr, R, st->nb, D.hs);
+    st->forest = true;
   });
 }
 
@@ -2280,16 +2441,21 @@ int wcb_forward_cached(wcb_handle* h, wcb_state* st, const int32_t* dec_ids, int
 }
 
 // ------------------------------------------------------------------------------ bias automaton
-int wcb_bias_create(wcb_handle* h, const int32_t* tokens, const int32_t* offsets, int n_phrases,
-                    const uint8_t* word_start, wcb_bias** out) {
-  return guarded(h, [&] {
-    REQUIRE(h && out && n_phrases >= 0 && (n_phrases == 0 || (tokens && offsets)), "bad argument");
-    const int V = h->d.vocab;
+// Aho-Corasick automaton of phrases [p0, p1) (phrase p = tokens[offsets[p] .. offsets[p + 1])), states
+// numbered from 0 = its root: trie depth and keep per state, trans(s) as CSR (local state ids), and the
+// gated root children (token, depth-1 state) in ascending token order.
+extern "C++" {
+namespace {
+struct HostAc {
+  std::vector<int> depth, keep, off, tok, dst;
+  std::vector<std::pair<int, int>> rc;
+};
+HostAc build_ac(const int32_t* tokens, const int32_t* offsets, int p0, int p1, int V, const uint8_t* word_start) {
     // trie
     std::vector<std::map<int, int>> ch(1);
     std::vector<int> depth(1, 0);
     std::vector<char> end(1, 0);
-    for (int p = 0; p < n_phrases; ++p) {
+    for (int p = p0; p < p1; ++p) {
       int s = 0;
       REQUIRE(offsets[p + 1] >= offsets[p], "offsets must be non-decreasing");
       for (int i = offsets[p]; i < offsets[p + 1]; ++i) {
@@ -2344,13 +2510,30 @@ int wcb_bias_create(wcb_handle* h, const int32_t* tokens, const int32_t* offsets
       off[s + 1] = (int)tok.size();
     }
     // root children: a match may START only at a word-start token (word_start == null: any token)
+    HostAc ac;
+    for (auto& kv : ch[0])
+      if (!word_start || word_start[kv.first]) ac.rc.emplace_back(kv.first, kv.second);
+    ac.depth = std::move(depth); ac.keep = std::move(keep);
+    ac.off = std::move(off); ac.tok = std::move(tok); ac.dst = std::move(dst);
+    return ac;
+}
+}  // namespace
+}  // extern "C++"
+
+int wcb_bias_create(wcb_handle* h, const int32_t* tokens, const int32_t* offsets, int n_phrases,
+                    const uint8_t* word_start, wcb_bias** out) {
+  return guarded(h, [&] {
+    REQUIRE(h && out && n_phrases >= 0 && (n_phrases == 0 || (tokens && offsets)), "bad argument");
+    const int V = h->d.vocab;
+    const HostAc ac = build_ac(tokens, offsets, 0, n_phrases, V, word_start);
+    const int ns = (int)ac.depth.size();
+    const std::vector<int>&depth = ac.depth, &keep = ac.keep, &off = ac.off, &tok = ac.tok, &dst = ac.dst;
     std::vector<uint32_t> bits((V + 31) / 32, 0u);
     std::vector<int> rc(V, -1);
-    for (auto& kv : ch[0])
-      if (!word_start || word_start[kv.first]) {
-        bits[kv.first >> 5] |= 1u << (kv.first & 31);
-        rc[kv.first] = kv.second;
-      }
+    for (auto& kv : ac.rc) {
+      bits[kv.first >> 5] |= 1u << (kv.first & 31);
+      rc[kv.first] = kv.second;
+    }
     auto b = std::make_unique<wcb_bias>();
     b->n_states = ns;
     b->vocab = V;
@@ -2404,6 +2587,55 @@ void wcb_bias_destroy(wcb_bias* b) {
 }
 
 int wcb_bias_num_states(const wcb_bias* b) { return b ? b->n_states : 0; }
+
+// ---- per-utterance bias lists: B automata in one state space (host data; wcb.h wcb_bias_batch)
+int wcb_bias_batch_create(wcb_handle* h, int B, const int32_t* tokens, const int32_t* phrase_off, const int32_t* clip_off,
+                          const uint8_t* word_start, wcb_bias_batch** out) {
+  return guarded(h, [&] {
+    REQUIRE(h && out && clip_off, "bad argument (handle, clip_off and out are required)");
+    REQUIRE(B >= 1 && B <= kForestClips, "bias batch: 1 <= B <= 64");
+    const int V = h->d.vocab;
+    REQUIRE(clip_off[0] >= 0, "clip_off must start at >= 0");
+    for (int b = 0; b < B; ++b) REQUIRE(clip_off[b + 1] >= clip_off[b], "clip_off must be non-decreasing");
+    const int P = clip_off[B];
+    REQUIRE(P == 0 || (tokens && phrase_off), "bad argument (tokens and phrase_off are required with phrases)");
+    if (P) REQUIRE(phrase_off[0] >= 0, "phrase_off must start at >= 0");
+    for (int p = 0; p < P; ++p) REQUIRE(phrase_off[p + 1] >= phrase_off[p], "phrase_off must be non-decreasing");
+    auto bb = std::make_unique<wcb_bias_batch>();
+    bb->B = B;
+    bb->vocab = V;
+    bb->rc_off.push_back(0);
+    bb->trans_off.push_back(0);
+    for (int b = 0; b < B; ++b) {
+      const HostAc ac = build_ac(tokens, phrase_off, clip_off[b], clip_off[b + 1], V, word_start);
+      const int s0 = (int)bb->st_depth.size(), t0 = (int)bb->trans_tok.size(), ns = (int)ac.depth.size();
+      bb->root.push_back(s0);
+      bb->n_states.push_back(ns);
+      bb->st_depth.insert(bb->st_depth.end(), ac.depth.begin(), ac.depth.end());
+      bb->st_keep.insert(bb->st_keep.end(), ac.keep.begin(), ac.keep.end());
+      for (int s = 1; s <= ns; ++s) bb->trans_off.push_back(t0 + ac.off[s]);
+      bb->trans_tok.insert(bb->trans_tok.end(), ac.tok.begin(), ac.tok.end());
+      for (int d : ac.dst) bb->trans_dst.push_back(s0 + d);
+      for (auto& kv : ac.rc) { bb->rc_tok.push_back(kv.first); bb->rc_dst.push_back(s0 + kv.second); }
+      bb->rc_off.push_back((int)bb->rc_tok.size());
+    }
+    *out = bb.release();
+  });
+}
+
+void wcb_bias_batch_destroy(wcb_bias_batch* bb) { delete bb; }
+
+int wcb_bias_batch_num_states(const wcb_bias_batch* bb, int clip) {
+  if (!bb) return 0;
+  if (clip < 0) return (int)bb->st_depth.size();
+  return clip < bb->B ? bb->n_states[clip] : 0;
+}
+
+int wcb_debug_counter(const wcb_handle* h, const char* name, int64_t* out) {
+  if (!h || !name || !out) return WCB_ERR_ARG;
+  if (!strcmp(name, "graph_captures")) { *out = h->n_graph_captures; return WCB_OK; }
+  return WCB_ERR_ARG;
+}
 
 int wcb_debug_copy(wcb_handle* h, const char* name, void* dst, int64_t bytes, int enc_layers) {
   return guarded(h, [&] {

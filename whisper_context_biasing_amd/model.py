@@ -87,6 +87,38 @@ class BiasList:
             self._h = None
 
 
+class BiasBatch:
+    """Per-utterance bias lists of one batch (wcb_bias_batch): clip b's own list of token-id sequences,
+    compiled on the host into one forest of automata. Host data: a decode call copies it, so it can be
+    dropped as soon as the call returns (also with block=False). Not cached: it is per call."""
+
+    def __init__(self, model: "WhisperCB", lists: Sequence[Sequence[Sequence[int]]]):
+        lib = _lib.load()
+        lists = [[list(map(int, p)) for p in L if len(p) > 0] for L in lists]
+        phrases = [p for L in lists for p in L]
+        toks = np.asarray([t for p in phrases for t in p] or [0], dtype=np.int32)
+        poff = np.zeros(len(phrases) + 1, dtype=np.int32)
+        poff[1:] = np.cumsum([len(p) for p in phrases]) if phrases else []
+        coff = np.zeros(len(lists) + 1, dtype=np.int32)
+        coff[1:] = np.cumsum([len(L) for L in lists]) if lists else []
+        ws = model.word_start
+        h = C.c_void_p()
+        _lib.check(lib.wcb_bias_batch_create(model._h, len(lists), toks.ctypes.data, poff.ctypes.data, coff.ctypes.data,
+                                             ws.ctypes.data if ws is not None else None, C.byref(h)),
+                   model._h, "wcb_bias_batch_create")
+        self._h = h
+        self._lib = lib
+        self.B = len(lists)
+        self.n_states = lib.wcb_bias_batch_num_states(h, -1)
+
+    def close(self):
+        if getattr(self, "_h", None) and getattr(self, "_lib", None) is not None:
+            self._lib.wcb_bias_batch_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+
 class StepDecoder:
     """One step-wise decode (WhisperCB.decode_begin). Greedy: step() -> (next ids [B] int32, scores [B] f32:
     the chosen token's logit + bias boost). Beam search (num_beams = nb > 1): step() -> (the token each
@@ -394,11 +426,41 @@ class WhisperCB:
                     out.append(list(toks))
         return out
 
+    def _spans_to_lists(self, bias_spans) -> List[List[List[int]]]:
+        """The collator tensor per sample (per_utterance_bias=True): row b's spans with the padding stripped
+        are clip b's list; the all-zeros [B, 1, 1] form gives empty lists."""
+        pad = self.collator_span_pad
+        arr = torch.as_tensor(bias_spans).cpu().numpy()
+        out = []
+        for sample in arr:
+            L, seen = [], set()
+            for span in sample:
+                toks = tuple(int(t) for t in span if int(t) != pad)
+                if toks and any(toks) and toks not in seen:
+                    seen.add(toks)
+                    L.append(list(toks))
+            out.append(L)
+        return out
+
+    def _clip_lists(self, bias_lists, bias_list, B: int) -> List[List[List[int]]]:
+        """bias_lists checked against the batch, a shared bias_list (phrases, not a prebuilt automaton)
+        concatenated into every clip's list."""
+        lists = [[list(map(int, p)) for p in L] for L in bias_lists]
+        if len(lists) != B:
+            raise ValueError(f"bias_lists has {len(lists)} lists, the batch {B} clips")
+        if bias_list is not None:
+            if isinstance(bias_list, BiasList):
+                raise ValueError("bias_lists takes a shared bias_list as phrases, not as a prebuilt BiasList")
+            shared = [list(map(int, p)) for p in bias_list]
+            lists = [L + shared for L in lists]
+        return lists
+
     # ---------------------------------------------------------------------------- generation
     def generate(self, input_features=None, labels=None, bias_spans=None, max_length: Optional[int] = None,
                  num_beams: Optional[int] = None, bias_list=None, bias_boost: float = 0.0,
                  min_new_tokens: int = 0, prompt_ids=None, return_dict_in_generate: bool = False,
-                 generation_config=None, use_graph: bool = True, block: bool = True, **kwargs):
+                 generation_config=None, use_graph: bool = True, block: bool = True, bias_lists=None,
+                 per_utterance_bias: bool = False, **kwargs):
         """Greedy (num_beams = 1, the reference's eval setting) or HF beam
         search (num_beams = 2..8, [tf] generation/utils.py:3208) on the device.
 
@@ -407,7 +469,12 @@ class WhisperCB:
 
         `labels` / `bias_spans` are accepted and ignored for token selection exactly like the
         reference (`[tf] trainer_seq2seq.py:310-329`), unless `bias_boost > 0` and no explicit
-        `bias_list` is given — then the batch's spans form the boosted bias list.
+        `bias_list` is given — then the batch's spans form the boosted bias list: their union over the
+        batch by default, or with `per_utterance_bias=True` row b's spans for clip b alone (a clip's
+        transcript then does not depend on its batch; a clip without spans is not boosted).
+
+        `bias_lists=[phrases of clip 0, ...]` (length B) boosts every clip with its own list
+        (wcb_generate_biased); a shared `bias_list` given with it is appended to every clip's list.
 
         `block=False` (serving pipelines): the caller's stream is not made to wait for the decode, so
         the next call's front end + encoder overlap this decode; the returned ids (and the inputs)
@@ -418,6 +485,10 @@ class WhisperCB:
         if not self._loaded:
             raise _lib.WcbError("weights not loaded")
         x_all = self._features(input_features)
+        if bias_lists is None and per_utterance_bias and bias_list is None and bias_boost > 0 and bias_spans is not None:
+            bias_lists = self._spans_to_lists(bias_spans)
+        if bias_lists is not None:   # checked on the whole batch, before any split
+            bias_lists, bias_list = self._clip_lists(bias_lists, bias_list, x_all.shape[0]), None
         nb_req = int(num_beams if num_beams is not None else getattr(generation_config or self.generation_config,
                                                                       "num_beams", 1) or 1)
         per_call = self.max_clips_per_call(nb_req)
@@ -428,9 +499,11 @@ class WhisperCB:
                       bias_list=bias_list, bias_boost=bias_boost, min_new_tokens=min_new_tokens,
                       prompt_ids=prompt_ids, return_dict_in_generate=return_dict_in_generate,
                       generation_config=generation_config, use_graph=use_graph, block=True)
-            if bias_list is None and bias_boost > 0 and bias_spans is not None:
+            if bias_lists is None and bias_list is None and bias_boost > 0 and bias_spans is not None:
                 kw["bias_list"], kw["bias_spans"] = self._spans_to_phrases(bias_spans), None
-            parts = [self.generate(x_all[i:i + per_call], **kw) for i in range(0, x_all.shape[0], per_call)]
+            parts = [self.generate(x_all[i:i + per_call],
+                                   bias_lists=bias_lists[i:i + per_call] if bias_lists is not None else None, **kw)
+                     for i in range(0, x_all.shape[0], per_call)]
             seqs = [p.sequences if return_dict_in_generate else p for p in parts]
             Wd = max(t.shape[1] for t in seqs)
             fill = self.dims.pad_token_id
@@ -451,7 +524,9 @@ class WhisperCB:
         if max_new < 1:
             raise ValueError("prompt leaves no room for new tokens")
         phrases = bias_list
-        if phrases is None and bias_boost > 0 and bias_spans is not None:
+        if bias_lists is not None:
+            phrases = None
+        elif phrases is None and bias_boost > 0 and bias_spans is not None:
             phrases = self._spans_to_phrases(bias_spans)
         if isinstance(phrases, BiasList):          # a prebuilt automaton (it must belong to this model)
             bl = phrases if bias_boost > 0 else None
@@ -461,10 +536,20 @@ class WhisperCB:
         out = torch.empty(B, max_new, dtype=torch.int32, device=self.device)
         steps = C.c_int32(0)
         pre = np.asarray(prefix, dtype=np.int32)
-        _lib.check(self._lib.wcb_generate(self._h, _ptr(x), B, C.byref(cfg), bl._h if bl else None,
-                                          pre.ctypes.data if len(prefix) > 1 else None, len(prefix),
-                                          _ptr(out), C.byref(steps), _stream(self.device)),
-                   self._h, "wcb_generate")
+        if bias_lists is not None and bias_boost > 0:
+            bb = BiasBatch(self, bias_lists)   # per call: not in the automaton LRU
+            try:
+                _lib.check(self._lib.wcb_generate_biased(self._h, _ptr(x), B, C.byref(cfg), bb._h,
+                                                         pre.ctypes.data if len(prefix) > 1 else None, len(prefix),
+                                                         _ptr(out), C.byref(steps), _stream(self.device)),
+                           self._h, "wcb_generate_biased")
+            finally:
+                bb.close()   # the call copied it (also with block=False)
+        else:
+            _lib.check(self._lib.wcb_generate(self._h, _ptr(x), B, C.byref(cfg), bl._h if bl else None,
+                                              pre.ctypes.data if len(prefix) > 1 else None, len(prefix),
+                                              _ptr(out), C.byref(steps), _stream(self.device)),
+                       self._h, "wcb_generate")
         if not block:
             return out[:, :steps.value]            # int32, valid after synchronize()
         ids = out[:, :steps.value].to(torch.int64)
@@ -474,12 +559,14 @@ class WhisperCB:
         return self._whisper_trim(ids)
 
     def decode_begin(self, encoder_outputs, prompt_ids=None, bias_list=None, bias_boost: float = 0.0,
-                     min_new_tokens: int = 0, num_beams: int = 1, max_length: Optional[int] = None) -> "StepDecoder":
+                     min_new_tokens: int = 0, num_beams: int = 1, max_length: Optional[int] = None,
+                     bias_lists=None) -> "StepDecoder":
         """Step-wise decoding from an encoder output [B, 1500, d] (this model's dtype, on its device): the
         streaming form of generate() (wcb_decode_begin / wcb_decode_begin_beams). Greedy (num_beams = 1) or
         beam search (num_beams 2..8; `max_length` = generate()'s, the beams' length cap: None = the
         max_target_positions cap). `prompt_ids` = one prompt for every clip or a [B, P] array of per-clip
-        prompts (decoder_start_token_id is appended as generate() does)."""
+        prompts (decoder_start_token_id is appended as generate() does). `bias_lists` = per-clip phrase lists as
+        generate() takes them (wcb_decode_bias_batch; a shared `bias_list` of phrases is appended to each)."""
         enc = self._encoder_state(encoder_outputs)   # [B, 1500, d] checked: the library copies B·1500·d
         B = enc.shape[0]
         if B > 64:
@@ -494,6 +581,8 @@ class WhisperCB:
             elif p.ndim != 2 or p.shape[0] != B:
                 raise ValueError(f"prompt_ids must be one prompt or a [{B}, P] array, got shape {p.shape}")
             pre = np.ascontiguousarray(np.concatenate([p, np.full((B, 1), start, np.int32)], axis=1))
+        if bias_lists is not None:
+            bias_lists, bias_list = self._clip_lists(bias_lists, bias_list, B), None
         if isinstance(bias_list, BiasList):   # a prebuilt automaton, as generate() accepts
             bl = bias_list if bias_boost > 0 else None
         else:
@@ -510,7 +599,14 @@ class WhisperCB:
                                                   pre.shape[1] if pre is not None else 1, float(bias_boost),
                                                   int(min_new_tokens), C.byref(st), _stream(self.device)), self._h,
                        "wcb_decode_begin")
-        return StepDecoder(self, st, B, bl, nb)
+        dec = StepDecoder(self, st, B, bl, nb)
+        if bias_lists is not None and bias_boost > 0:
+            bb = BiasBatch(self, bias_lists)
+            try:
+                _lib.check(self._lib.wcb_decode_bias_batch(self._h, st, bb._h), self._h, "wcb_decode_bias_batch")
+            finally:
+                bb.close()
+        return dec
 
     @staticmethod
     def max_clips_per_call(num_beams: int = 1) -> int:
@@ -539,6 +635,12 @@ class WhisperCB:
         return out
 
     kRetiredMax = 32
+
+    def debug_counter(self, name: str) -> int:
+        """wcb_debug_counter: e.g. "graph_captures", the decode graphs instantiated so far."""
+        v = C.c_int64(0)
+        _lib.check(self._lib.wcb_debug_counter(self._h, name.encode(), C.byref(v)), self._h, f"wcb_debug_counter({name})")
+        return v.value
 
     def synchronize(self):
         """Wait for every queued front-end / encoder / decode operation of this model (and release the
