@@ -271,6 +271,35 @@ int wcb_generate_biased(wcb_handle* h, const float* mel, int B, const wcb_gen_cf
  * given bias = NULL (a non-NULL bias is WCB_ERR_ARG). */
 int wcb_decode_bias_batch(wcb_handle* h, wcb_state* st, const wcb_bias_batch* bb);
 
+/* Token log-probabilities and sequence scores.
+ *  - token log-prob (greedy): logprob[b][t] = logit[b][t][tok] − logsumexp_v(logit[b][t][v]) over the RAW f32
+ *    logits of step t — the model's own distribution. The bias boost and the min_new_tokens EOS mask change
+ *    which token is chosen; they never enter the log-prob (a phrase forced in by lambda shows as a low log-prob
+ *    under a boosted token). A position where an already finished row emits pad holds 0.0f; the EOS a row
+ *    emits itself carries its real log-prob. Computed on chip: the LM head keeps per (row, workgroup) online-
+ *    softmax partials (max, Σ exp(v − max)) of the columns it walks beside its argmax partials, and the
+ *    selection kernel merges them in a fixed order (deterministic for a given "lm_walkers").
+ *  - sequence score (beam search): seq_score[b] = the score of the returned (best finished) hypothesis of clip
+ *    b, HF's sequences_scores: the length-normalised sum of its processed (boosted) token log-probs.
+ *  - With both off every existing path launches exactly what it launched before; with log-probs on the
+ *    selected ids are bit-identical to the same call with them off, in every dtype.
+ * wcb_generate_scored: wcb_generate (bias, bb = NULL) / wcb_generate_biased (bb) with the scores; at most one of
+ * bias / bb non-NULL (else WCB_ERR_ARG). Greedy: out_logprobs f32 DEVICE [B][cfg->max_new_tokens], laid out and
+ * copied out like out_ids (async_out included), out_seq_scores must be NULL. Beams: out_seq_scores f32 DEVICE
+ * [B], out_logprobs must be NULL. The wrong pointer for the mode: WCB_ERR_UNSUPPORTED. Both NULL: exactly
+ * wcb_generate / wcb_generate_biased. A scored greedy decode replays a captured graph of its own, kept beside
+ * the unscored one of its decode context. */
+int wcb_generate_scored(wcb_handle* h, const float* mel, int B, const wcb_gen_cfg* cfg, const wcb_bias* bias,
+                        const wcb_bias_batch* bb, const int32_t* prefix, int prefix_len, int32_t* out_ids,
+                        float* out_logprobs, float* out_seq_scores, int32_t* out_steps, void* stream);
+/* step-wise: after wcb_decode_begin and before the first wcb_decode_step, on a greedy state (a beam-search
+ * state: WCB_ERR_UNSUPPORTED; after a step or on a forward cache: WCB_ERR_STATE). Every step then also records
+ * the log-prob of the token it chose. */
+int wcb_decode_enable_logprobs(wcb_handle* h, wcb_state* st);
+/* shaped like wcb_decode_result: out [B][out_ld] (f32, DEVICE) receives the log-probs of the n steps taken so
+ * far, *out_steps (host) = n; out_ld < n is WCB_ERR_ARG; log-probs not enabled: WCB_ERR_STATE. */
+int wcb_decode_logprobs(wcb_handle* h, wcb_state* st, float* out, int out_ld, int32_t* out_steps, void* stream);
+
 /* debug counters by name (not part of wcb_profile_read): "graph_captures" = decode graphs instantiated so
  * far on this handle. Unknown name: WCB_ERR_ARG. */
 int wcb_debug_counter(const wcb_handle* h, const char* name, int64_t* out);
@@ -289,7 +318,8 @@ int wcb_profile_read(wcb_handle* h, int n, char (*names)[32], int64_t* launches,
  * launched nothing or was stamped on the device */
 int wcb_profile_kernel(wcb_handle* h, int i, char* name, int cap, int64_t* grid);
 
-/* debug: copy an internal workspace buffer (xt, hbuf, x, h, qkv, att, ffn, encout, xkv, logits)
+/* debug: copy an internal workspace buffer (xt, hbuf, x, h, qkv, att, ffn, encout, xkv, logits; step_logits:
+ * the step-wise decode's last logits rows, row stride = vocab rounded up to a multiple of 128)
  * into dst (device) after synchronising; enc_layers limits later encodes to that many layers
  * (-1 = all). bytes == 0 only sets the limit. */
 int wcb_debug_copy(wcb_handle* h, const char* name, void* dst, int64_t bytes, int enc_layers);
@@ -314,6 +344,14 @@ int wcb_op_gemm_kernel(int dtype, const void* A, const void* W, int M, int N, in
 int wcb_op_gemm_ln(int dtype, const float* X, const float* ln_w, const float* ln_b, const float* stats,
                    const void* W, int M, int N, int K, const float* bias, int act, void* out, int out_f32,
                    void* stream);
+/* the greedy LM head with its softmax partials, then the partial merge (no LayerNorm, no boost, no EOS mask):
+ * A [M][K], W [V][K] in dtype (M <= 64) → logits f32 [M][ld] (ld >= V), lse[M] = logsumexp of each logits row,
+ * argmax[M] (lowest index on ties). Runs the kernels the decode step runs for that dtype / K / M: the column
+ * walk with `walkers` workgroups per row block (0: the kernel default; 16-bit at K = 64, 512, 768, 1024, 1280
+ * on a fragment-major copy of W, as the runtime's) for K = 64 .. 1280, the older skinny kernel's 64-column
+ * epilogue for K = 32 and 2560; another K is WCB_ERR_UNSUPPORTED. Blocks until done (it owns scratch buffers). */
+int wcb_op_lm_head_lse(int dtype, const void* A, const void* W, int M, int V, int K, int walkers, float* logits, long ld,
+                       float* lse, int32_t* argmax, void* stream);
 /* y[M][d] (dtype) = LayerNorm(x f32 [M][d]) * w + b, eps 1e-5 */
 int wcb_op_layernorm(int dtype, const float* x, const float* w, const float* b, void* y, int M, int d,
                      void* stream);

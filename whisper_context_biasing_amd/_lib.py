@@ -67,6 +67,11 @@ SIGNATURES = {
     "wcb_generate_biased": (C.c_int, [_P, _P, C.c_int, C.POINTER(WcbGenCfg), _P, _P, C.c_int, _P,
                                       C.POINTER(C.c_int32), _P]),
     "wcb_decode_bias_batch": (C.c_int, [_P, _P, _P]),
+    "wcb_generate_scored": (C.c_int, [_P, _P, C.c_int, C.POINTER(WcbGenCfg), _P, _P, _P, C.c_int, _P, _P, _P,
+                                      C.POINTER(C.c_int32), _P]),
+    "wcb_decode_enable_logprobs": (C.c_int, [_P, _P]),
+    "wcb_decode_logprobs": (C.c_int, [_P, _P, _P, C.c_int, C.POINTER(C.c_int32), _P]),
+    "wcb_op_lm_head_lse": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_long, _P, _P, _P]),
     "wcb_debug_counter": (C.c_int, [_P, C.c_char_p, C.POINTER(C.c_int64)]),
     "wcb_debug_copy": (C.c_int, [_P, C.c_char_p, _P, C.c_int64, C.c_int]),
     "wcb_profile_enable": (C.c_int, [_P, C.c_int]),

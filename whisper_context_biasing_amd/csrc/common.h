@@ -103,6 +103,18 @@ WCB_DEV void group_arrive_wait(unsigned long long* cnt, unsigned long long n, in
 // fused multiply-add, so every kernel rounds exactly like the oracle
 WCB_DEV float bias_bonus(float x, float lam, int units) { return __fadd_rn(x, __fmul_rn(lam, (float)units)); }
 
+// Online-softmax partials of the token log-probs: a pair (m, s) stands for Σ exp(v) = s·exp(m) over the
+// values seen, s = Σ exp(v − m); (−inf, 0) is the empty pair. The larger maximum's sum is kept as it is and
+// the other one rescaled, so a value joining at the maximum costs no rounding of the sum so far.
+WCB_DEV void lse_merge(float& m, float& s, float om, float os) {
+  const float nm = fmaxf(m, om);
+  const float e = nm == -INFINITY ? 0.f : expf(-fabsf(m - om));   // (both empty: no inf − inf)
+  s = m >= om ? fmaf(os, e, s) : fmaf(s, e, os);
+  m = nm;
+}
+// one more value
+WCB_DEV void lse_push(float& m, float& s, float v) { lse_merge(m, s, v, 1.f); }
+
 WCB_DEV f32x4 mma16(const s16x8& a, const s16x8& b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }

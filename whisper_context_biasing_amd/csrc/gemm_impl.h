@@ -1122,6 +1122,18 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(GemmArgs g) {
         g.sel_val[(long)row * gridDim.x + blockIdx.x] = x;
         g.sel_idx[(long)row * gridDim.x + blockIdx.x] = xi;
       }
+      if (g.sel_max) {   // token log-probs: the softmax partial of the row's 64 raw values (invalid lanes: empty)
+        float pm = valid ? v : -INFINITY, ps = valid ? 1.f : 0.f;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+          const float om = __shfl_xor(pm, o, 64), os = __shfl_xor(ps, o, 64);
+          lse_merge(pm, ps, om, os);
+        }
+        if (lane == 0 && row < g.M) {
+          g.sel_max[(long)row * gridDim.x + blockIdx.x] = pm;
+          g.sel_sum[(long)row * gridDim.x + blockIdx.x] = ps;
+        }
+      }
     }
   }
 }
@@ -1302,6 +1314,12 @@ __global__ __launch_bounds__(NW * 64) void gemm_dec_kernel(GemmArgs g) {
   int sel_bi[EP];
 #pragma unroll
   for (int it = 0; it < EP; ++it) { sel_best[it] = -INFINITY; sel_bi[it] = 0x7fffffff; }
+  // token log-probs (sel_max non-null; wave-uniform): every thread's running softmax pair over the raw values
+  // of its (row, column-in-tile) outputs along the walk; the 16 lanes of a row merge once, after the walk
+  const bool lse_on = g.sel_max != nullptr;
+  float lse_m[EP], lse_s[EP];
+#pragma unroll
+  for (int it = 0; it < EP; ++it) { lse_m[it] = -INFINITY; lse_s[it] = 0.f; }
   // bias-boost root bits of the tile's 16 columns (one 32-bit word: tiles are 16-aligned), fetched one
   // tile ahead with the weights (read in the epilogue they cost a dependent round trip per tile)
   const bool boost = g.sel_val && g.sel_lam != 0.f;
@@ -1396,6 +1414,9 @@ __global__ __launch_bounds__(NW * 64) void gemm_dec_kernel(GemmArgs g) {
         }
         // tiles are walked in increasing column order: a later tile wins only when strictly better
         if (x > sel_best[it]) { sel_best[it] = x; sel_bi[it] = xi; }
+        if (lse_on) {   // the raw value v: before the boost and the EOS mask; an invalid lane adds nothing
+          if (valid) lse_push(lse_m[it], lse_s[it], v);
+        }
       }
     }
     buf ^= 1;
@@ -1418,6 +1439,22 @@ __global__ __launch_bounds__(NW * 64) void gemm_dec_kernel(GemmArgs g) {
       if ((o & 15) == 0 && o < R * 16 && row < g.M) {
         g.sel_val[(long)row * gridDim.x + blockIdx.x] = sel_best[it];
         g.sel_idx[(long)row * gridDim.x + blockIdx.x] = sel_bi[it];
+      }
+    }
+    if (lse_on) {   // one softmax partial per (row, workgroup), the row's 16 lanes merged in butterfly order
+#pragma unroll
+      for (int it = 0; it < EP; ++it) {
+        float pm = lse_m[it], ps = lse_s[it];
+#pragma unroll
+        for (int x2 = 1; x2 < 16; x2 <<= 1) {
+          const float om = __shfl_xor(pm, x2, 64), os = __shfl_xor(ps, x2, 64);
+          lse_merge(pm, ps, om, os);
+        }
+        const int o = it * NT + tid, row = mb + (o >> 4);
+        if ((o & 15) == 0 && o < R * 16 && row < g.M) {
+          g.sel_max[(long)row * gridDim.x + blockIdx.x] = pm;
+          g.sel_sum[(long)row * gridDim.x + blockIdx.x] = ps;
+        }
       }
     }
   }

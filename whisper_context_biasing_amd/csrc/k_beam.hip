@@ -634,7 +634,10 @@ __global__ __launch_bounds__(256) void beam_output_kernel(BeamArgs a) {
   const int len = a.fin_len[r];
   for (int t = threadIdx.x; t < a.out_ld; t += blockDim.x)
     a.out_ids[(long)b * a.out_ld + t] = (t < len && t < Lg) ? a.fin_seq[(long)r * Lg + t] : a.pad;
-  if (threadIdx.x == 0) atomicMax(a.out_len, len);
+  if (threadIdx.x == 0) {
+    atomicMax(a.out_len, len);
+    if (a.out_score) a.out_score[b] = a.fin_sc[r];   // the returned hypothesis's score (HF sequences_scores)
+  }
 }
 
 void beam_init(const BeamArgs& a, hipStream_t s) {

@@ -30,6 +30,19 @@ namespace wcb {
 
 WCB_DEV bool better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
 
+// One wave merges a row's n softmax partials (common.h lse_merge) in a fixed order — lane-strided, then the xor
+// butterfly, as the argmax partials — into (m, s) on every lane: logsumexp of the row = m + log(s).
+WCB_DEV void merge_lse_partials(const float* pm, const float* ps, int n, int lane, float& m, float& s) {
+  m = -INFINITY;
+  s = 0.f;
+  for (int c = lane; c < n; c += 64) lse_merge(m, s, pm[c], ps[c]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float om = __shfl_xor(m, o, 64), os = __shfl_xor(s, o, 64);
+    lse_merge(m, s, om, os);
+  }
+}
+
 __global__ __launch_bounds__(256) void select_partial_kernel(SelectArgs a) {
   const int m = blockIdx.y, c = blockIdx.x;
   const int chunk = (a.V + a.nchunk - 1) / a.nchunk;
@@ -82,6 +95,9 @@ __global__ __launch_bounds__(64) void select_finalize_kernel(SelectArgs a) {
     const int i = a.part_idx[m * a.nchunk + c];
     if (better(v, i, bv, bi)) { bv = v; bi = i; }
   }
+  // token log-probs: the row's softmax partials in the same fixed order (lane-strided, then the butterfly)
+  float lm = -INFINITY, ls = 0.f;
+  if (a.out_logprob) merge_lse_partials(a.part_max + (long)m * a.nchunk, a.part_sum + (long)m * a.nchunk, a.nchunk, lane, lm, ls);
   const int s = a.state[m];
   const int t0 = a.trans_off[s], t1 = a.trans_off[s + 1];
   if (a.lam != 0.f) {
@@ -178,6 +194,8 @@ __global__ __launch_bounds__(64) void select_finalize_kernel(SelectArgs a) {
     a.next_ids[m] = tok;
     a.out_ids[(long)m * a.out_ld + step] = tok;
     if (a.out_score) a.out_score[m] = fin ? 0.f : bv;
+    if (a.out_logprob)   // the chosen token's raw logit against the row's logsumexp
+      a.out_logprob[(long)m * a.out_ld + step] = fin ? 0.f : a.logits[(long)m * a.ld + tok] - (lm + logf(ls));
     const bool nf = fin || tok == a.eos;
     a.finished[m] = nf ? 1 : 0;
     // one 64-bit counter: arrivals in the low word, unfinished rows in the high word, so the row that
@@ -270,6 +288,36 @@ __global__ void forest_init_kernel(ForestArgs f, int* state, int* rowbase, int R
 }
 void forest_init(const ForestArgs& f, int* state, int* rowbase, int R, int nb, hipStream_t s) {
   WCB_LAUNCH(forest_init_kernel, dim3((R + 255) / 256), dim3(256), 0, s, f, state, rowbase, R, nb);
+}
+
+// The partial merges of select_finalize_kernel on their own (wcb_op_lm_head_lse): one wave per row,
+// argmax[m] = the best partial (lowest index on ties), lse[m] = max + log(sum) of the merged softmax partials.
+__global__ __launch_bounds__(64) void lse_finalize_kernel(const float* part_val, const int* part_idx, const float* part_max,
+                                                          const float* part_sum, int nchunk, float* lse, int* argmax) {
+  const int m = blockIdx.x, lane = threadIdx.x;
+  float bv = -INFINITY;
+  int bi = 0x7fffffff;
+  for (int c = lane; c < nchunk; c += 64) {
+    const float v = part_val[m * nchunk + c];
+    const int i = part_idx[m * nchunk + c];
+    if (better(v, i, bv, bi)) { bv = v; bi = i; }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(bv, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    if (better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+  }
+  float lm, ls;
+  merge_lse_partials(part_max + (long)m * nchunk, part_sum + (long)m * nchunk, nchunk, lane, lm, ls);
+  if (lane == 0) {
+    argmax[m] = bi;
+    lse[m] = lm + logf(ls);
+  }
+}
+void lm_head_lse_finalize(const float* part_val, const int* part_idx, const float* part_max, const float* part_sum, int M,
+                          int nchunk, float* lse, int* argmax, hipStream_t s) {
+  WCB_LAUNCH(lse_finalize_kernel, dim3(M), dim3(64), 0, s, part_val, part_idx, part_max, part_sum, nchunk, lse, argmax);
 }
 
 void select_greedy(const SelectArgs& a, hipStream_t s) {

@@ -66,6 +66,10 @@ struct GemmArgs {
   const uint32_t* sel_root_bits = nullptr; float sel_lam = 0.f;
   const int* sel_rowbase = nullptr;   // per row k - d of its bias state: bonus lam·(base + root bit)
   int sel_eos = -1; const int* sel_step = nullptr; int sel_min_new = 0;
+  // LM head, token log-probs (nullable, with sel_val; laid out like it): per (row, workgroup) the online-softmax
+  // pair (max, Σ exp(v − max)) of the RAW logits v of the workgroup's columns — before the boost and the EOS
+  // mask; columns >= N and rows >= M contribute nothing (a workgroup without a valid column: (−inf, 0))
+  float* sel_max = nullptr; float* sel_sum = nullptr;
   // grouped A (skinny path, block-diagonal weights): the A row of output column block n0 starts
   // (n0 / a_grp_n) · a_grp_off elements further (q'_h = W_k,hᵀ q_h: K = 64 columns of head h)
   int a_grp_n = 0; long a_grp_off = 0;
@@ -257,6 +261,12 @@ struct SelectArgs {
   int* all_done = nullptr;
   unsigned long long* ticket_unfin = nullptr;   // arrivals | unfinished << 32, zero between steps (reset by the last row)
   float* out_score = nullptr;        // optional: the chosen token's (boosted) logit per row (0 for finished rows)
+  // token log-probs (out_logprob non-null): the LM head's softmax partials [M][nchunk] (GemmArgs::sel_max /
+  // sel_sum) merged per row in a fixed order, lse = max + log(sum); out_logprob[m·out_ld + step] =
+  // logits[m][tok] − lse, the model's own log-prob of the chosen token (raw logits: no boost, no EOS mask),
+  // 0 for a row that had finished before this step
+  const float* part_max = nullptr; const float* part_sum = nullptr;
+  float* out_logprob = nullptr;
   // the next step's embedding written by the finalize (emb non-null; DType dtype): x [M][d] f32 =
   // emb[tok] + pemb[min(pos + 1, n_pos - 1)], its T copy x16, the fragment-major T copy x16fm (fm_nw,
   // fm_kpw; nullable) and the per-st_w-column (Σx, Σx²) partials st (nullable) — embed()'s outputs bit
@@ -269,6 +279,9 @@ struct SelectArgs {
 };
 void select_greedy(const SelectArgs& a, hipStream_t s);          // vocabulary pass + finalize
 void select_finalize(const SelectArgs& a, hipStream_t s);        // partials already written (fused LM head)
+// the finalize's partial merges alone, [M][nchunk] partials → lse[M], argmax[M] (wcb_op_lm_head_lse)
+void lm_head_lse_finalize(const float* part_val, const int* part_idx, const float* part_max, const float* part_sum, int M,
+                          int nchunk, float* lse, int* argmax, hipStream_t s);
 void advance_forced(int* next_ids, const int* forced, int M, int ld, int* pos, hipStream_t s);
 void gather_col(int* dst, const int* src, int M, int ld, int col, hipStream_t s);
 
@@ -297,7 +310,8 @@ struct BeamArgs {
   float* fin_sc = nullptr; int* fin_done = nullptr; int* fin_len = nullptr; int* fin_seq = nullptr;  // [B·nb](·(Lt-P))
   int* flags = nullptr;                                 // [B][2]: heuristic unsatisfied, all K hit
   int* out_ids = nullptr; int out_ld = 0; int* out_len = nullptr;
-  int* parent = nullptr;                                // [R] (nullable): the beam each running beam extends
+  float* out_score = nullptr;                           // [B] (nullable): fin_sc of the hypothesis beam_output returns
+  int* parent = nullptr;                               // [R] (nullable): the beam each running beam extends
   ForestArgs forest;                                    // per-utterance lists (forest.root non-null): clip = row / nb
 };
 void beam_init(const BeamArgs& a, hipStream_t s);

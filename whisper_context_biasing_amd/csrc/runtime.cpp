@@ -163,6 +163,20 @@ struct DecCtx {
   int* done_h = nullptr;                        // pinned: the "all rows finished" step of the last 2 chunks
   hipEvent_t ev_poll[2] = {};
   std::string gkey;
+  // token log-probs (wcb_generate_scored, wcb_decode_enable_logprobs): the LM head's softmax partials
+  // [rows][nchunk] beside part_val, the log-prob rows [rows][out_ld] beside outbuf — allocated by the first
+  // scored call — and the scored decode's own graphs, so scored and unscored calls each replay theirs
+  DevBuf part_max, part_sum, lpbuf;
+  hipGraphExec_t gexec_lp = nullptr, gexec_k_lp = nullptr;
+  std::string gkey_lp;
+  void drop_graphs() {
+    for (hipGraphExec_t* g : {&gexec, &gexec_k, &gexec_lp, &gexec_k_lp}) {
+      if (*g) (void)hipGraphExecDestroy(*g);
+      *g = nullptr;
+    }
+    gkey.clear();
+    gkey_lp.clear();
+  }
   // per-utterance bias forest of the call decoding in this context: device buffer carved by the capacities
   // (states, transitions, root children; they only grow: quiesce + realloc, the graph key names them), the
   // pinned staging copy the asynchronous upload reads, and the event of the last upload from it
@@ -639,10 +653,10 @@ void wcb_destroy(wcb_handle* h) {
   (void)hipDeviceSynchronize();
   for (wcb_bias* b : h->biases) b->owner = nullptr;   // still valid to destroy; no graph holds them now
   for (DecCtx& D : h->dc) {
-    if (D.gexec) (void)hipGraphExecDestroy(D.gexec);
-    if (D.gexec_k) (void)hipGraphExecDestroy(D.gexec_k);
+    D.drop_graphs();
     for (DevBuf* b : {&D.kvself, &D.dx, &D.dx16, &D.dx16fm, &D.dh, &D.dq, &D.dqp, &D.du, &D.datt, &D.dffn, &D.dstats, &D.drst, &D.xpart, &D.xml, &D.xticket,
-                      &D.logits, &D.part_val, &D.part_idx, &D.ints, &D.outbuf, &D.forced, &D.beam, &D.kq_cnt})
+                      &D.logits, &D.part_val, &D.part_idx, &D.ints, &D.outbuf, &D.forced, &D.beam, &D.kq_cnt, &D.part_max, &D.part_sum,
+                      &D.lpbuf})
       b->release();
     if (D.ev_fork) (void)hipEventDestroy(D.ev_fork);
     for (hipEvent_t e : D.ev_poll)
@@ -1175,12 +1189,7 @@ void encode_impl(wcb_handle* h, const float* mel, int B, void* enc_out) {
 enum { I_STEP = 0, I_POS = 1, I_DONE = 2, I_TICKET = 3, I_UNFIN = 4, I_TU = 6, I_NEXT = 16 };
 
 void drop_graphs(wcb_handle* h) {
-  for (DecCtx& D : h->dc) {
-    if (D.gexec) (void)hipGraphExecDestroy(D.gexec);
-    if (D.gexec_k) (void)hipGraphExecDestroy(D.gexec_k);
-    D.gexec = D.gexec_k = nullptr;
-    D.gkey.clear();
-  }
+  for (DecCtx& D : h->dc) D.drop_graphs();
 }
 
 // positions per prefill pass: up to kPrefillRows activation rows (bounds the row workspaces)
@@ -1260,6 +1269,18 @@ void ensure_dec_ws(wcb_handle* h, int clips, int B, int T, int out_ld, int xmode
   }
 }
 
+// token log-probs: the scored decode's buffers of context D for B rows of out_ld columns (partials sized
+// with D.nchunk, like part_val); a reallocation drains the streams and drops the context's graphs
+void ensure_lp_ws(wcb_handle* h, DecCtx& D, int B, int out_ld) {
+  const size_t np = (size_t)std::max(B, D.dec_B) * D.nchunk * 4, nl = (size_t)B * out_ld * 4;
+  if (np <= D.part_max.bytes && np <= D.part_sum.bytes && nl <= D.lpbuf.bytes) return;
+  quiesce(h);
+  D.drop_graphs();
+  D.part_max.ensure(np);
+  D.part_sum.ensure(np);
+  D.lpbuf.ensure(nl);
+}
+
 // cross-attention K/V of every decoder layer from the encoder output (A4), once per clip:
 // one GEMM [B·1500, d] × [2·L·d, d]ᵀ written head-split as [L·2][B][H][1500][64]
 void cross_kv(wcb_handle* h, int B, int buf, const void* enc) {
@@ -1300,6 +1321,9 @@ struct StepCfg {
   // step_embed before the first step), and this step's finalize writes the next one
   bool embedded = false;
   const ForestDev* forest = nullptr;   // per-utterance bias lists (bias = the empty automaton then: zero root bitmap)
+  // greedy select, token log-probs: [B][out_ld] f32 beside the ids (the context's lpbuf; ensure_lp_ws) — the LM
+  // head then also writes its softmax partials and the finalize merges them. Null: the step as it always was
+  float* logprob_out = nullptr;
 };
 
 // the residual's fragment-major copy applies (lean path): the lean LayerNorm table covers d, every
@@ -1572,6 +1596,10 @@ void decode_rows(wcb_handle* h, const StepCfg& c, int b0, int nb, int chain, hip
       lm.sel_root_bits = c.bias->root_bits.as<uint32_t>(); lm.sel_lam = c.lam;
       lm.sel_rowbase = ints + I_NEXT + 3 * c.B + b0;   // per row k - d of its state (select_finalize)
       lm.sel_eos = h->d.eos_token_id; lm.sel_step = ints + I_STEP; lm.sel_min_new = c.min_new;
+      if (c.logprob_out) {   // token log-probs: the softmax partials of the raw logits beside the argmax ones
+        lm.sel_max = D.part_max.as<float>() + (size_t)b0 * D.nchunk;
+        lm.sel_sum = D.part_sum.as<float>() + (size_t)b0 * D.nchunk;
+      }
     }
     if (lm_tiled) {
       proj("lm_head", lm);
@@ -1647,6 +1675,9 @@ void decode_step(wcb_handle* h, const StepCfg& c) {
     s.all_done = ints + I_DONE;
     s.ticket_unfin = reinterpret_cast<unsigned long long*>(ints + I_TU);
     s.out_score = c.score_out;
+    if (c.logprob_out) {
+      s.part_max = D.part_max.as<float>(); s.part_sum = D.part_sum.as<float>(); s.out_logprob = c.logprob_out;
+    }
     if (c.embedded) {   // the next step's input embedding in the same launch (embed()'s outputs)
       const bool r32 = h->dec_gemm && lnf_possible(h);
       s.emb = h->tok_emb; s.pemb = h->dec_pos; s.n_pos = h->d.n_text_ctx; s.d = d; s.dtype = h->dt;
@@ -1845,12 +1876,16 @@ int wcb_encode(wcb_handle* h, const float* mel, int B, void* enc_out, void* stre
 // wcb_generate / wcb_generate_biased: one shared automaton `bias` (or none), or the per-utterance forest `bb`
 static void generate_impl(wcb_handle* h, const float* mel, int B, const wcb_gen_cfg* cfg, const wcb_bias* bias,
                           const wcb_bias_batch* bb, const int32_t* prefix, int prefix_len, int32_t* out_ids,
-                          int32_t* out_steps, void* stream) {
+                          int32_t* out_steps, void* stream, float* out_logprobs = nullptr, float* out_seq_scores = nullptr) {
   {
     REQUIRE(h && cfg && out_ids && out_steps && B > 0, "bad argument");
     if (!h->ready) throw WcbError(WCB_ERR_STATE, "weights not finalized");
     const int nb = cfg->num_beams;
     REQUIRE(nb >= 1 && nb <= kMaxBeams, "num_beams must be in [1, 8]");
+    if (nb > 1 && out_logprobs)
+      throw WcbError(WCB_ERR_UNSUPPORTED, "token log-probs are greedy only (beam search: out_seq_scores)");
+    if (nb == 1 && out_seq_scores)
+      throw WcbError(WCB_ERR_UNSUPPORTED, "sequence scores are beam-search only (greedy: out_logprobs)");
     const int R = B * nb;   // decoder rows: utterance b, beam i -> row b*nb + i
     REQUIRE(B <= 64, "batch > 64 per handle: split the batch");
     REQUIRE(R <= 64 * DecCtx::kMaxSub, "batch x num_beams > 512 rows per call: split the batch");
@@ -1883,6 +1918,7 @@ static void generate_impl(wcb_handle* h, const float* mel, int B, const wcb_gen_
     DecCtx& D = h->dc[buf];
     // beam state [R] / [R][max_new] / [R][Tc] / [R][K] / [B][2] in one buffer
     if (nb > 1) ensure_beam_buf(h, D, B, nb, cfg->max_new_tokens, Tc);
+    if (out_logprobs) ensure_lp_ws(h, D, R, out_ld);
     // ---- encoder stream: front end → encoder → cross-K/V into buffer `buf` once the decode that
     //      last read that buffer has finished. It overlaps the previous call's decode.
     sync_in(h, stream, h->he);
@@ -1924,6 +1960,10 @@ static void generate_impl(wcb_handle* h, const float* mel, int B, const wcb_gen_
     sc.nb = nb;
     sc.xmode = xm;
     if (nb > 1) { sc.phys = bm.phys; sc.beam = &bm; }
+    if (out_logprobs) {   // every column a step does not reach stays 0
+      sc.logprob_out = D.lpbuf.as<float>();
+      HIPCHK(hipMemsetAsync(D.lpbuf.p, 0, (size_t)R * out_ld * 4, D.hs));
+    }
     // prompt positions 0 .. P-2 in causal prefill passes, then the last prompt token is the first
     // decode step's input
     for (int p0 = 0, np; p0 + 1 < P; p0 += np) {
@@ -1953,9 +1993,13 @@ static void generate_impl(wcb_handle* h, const float* mel, int B, const wcb_gen_
     // "all finished" flag once per chunk.
     const int chunk = h->steps_per_graph;
     int done = 0, steps = 0;
-    if (use_graph && (!D.gexec || D.gkey != key)) {
-      if (D.gexec) { (void)hipGraphExecDestroy(D.gexec); D.gexec = nullptr; }
-      if (D.gexec_k) { (void)hipGraphExecDestroy(D.gexec_k); D.gexec_k = nullptr; }
+    // (a scored decode has its own graphs and key: neither kind of call evicts the other's)
+    hipGraphExec_t& gexec = out_logprobs ? D.gexec_lp : D.gexec;
+    hipGraphExec_t& gexec_k = out_logprobs ? D.gexec_k_lp : D.gexec_k;
+    std::string& gkey = out_logprobs ? D.gkey_lp : D.gkey;
+    if (use_graph && (!gexec || gkey != key)) {
+      if (gexec) { (void)hipGraphExecDestroy(gexec); gexec = nullptr; }
+      if (gexec_k) { (void)hipGraphExecDestroy(gexec_k); gexec_k = nullptr; }
       const int ks[2] = {1, chunk};
       for (int ki = 0; ki < (chunk > 1 ? 2 : 1); ++ki) {   // the k-step graph only when it differs
         const int k = ks[ki];
@@ -1963,11 +2007,11 @@ static void generate_impl(wcb_handle* h, const float* mel, int B, const wcb_gen_
         HIPCHK(hipStreamBeginCapture(D.hs, hipStreamCaptureModeThreadLocal));
         for (int i = 0; i < k; ++i) decode_step(h, sc);
         HIPCHK(hipStreamEndCapture(D.hs, &graph));
-        HIPCHK(hipGraphInstantiate(k == 1 ? &D.gexec : &D.gexec_k, graph, nullptr, nullptr, 0));
+        HIPCHK(hipGraphInstantiate(k == 1 ? &gexec : &gexec_k, graph, nullptr, nullptr, 0));
         ++h->n_graph_captures;
         HIPCHK(hipGraphDestroy(graph));
       }
-      D.gkey = key;
+      gkey = key;
     }
     // Natural-EOS mode (reference decoding) polls the device "all finished" step one chunk behind:
     // chunk k+1 is queued before the host waits for chunk k's flag, so the GPU never idles on the
@@ -1976,12 +2020,12 @@ static void generate_impl(wcb_handle* h, const float* mel, int B, const wcb_gen_
     h->timed_wall("decode_loop", D.hs, [&] {
       while (steps < max_new) {
         const int n = std::min(chunk, max_new - steps);
-        if (use_graph && n == chunk && D.gexec_k) {
-          HIPCHK(hipGraphLaunch(D.gexec_k, D.hs));
+        if (use_graph && n == chunk && gexec_k) {
+          HIPCHK(hipGraphLaunch(gexec_k, D.hs));
         } else {
           for (int i = 0; i < n; ++i) {
             if (use_graph) {
-              HIPCHK(hipGraphLaunch(D.gexec, D.hs));
+              HIPCHK(hipGraphLaunch(gexec, D.hs));
             } else {
               sc.host_pos = P - 1 + steps + i;
               decode_step(h, sc);
@@ -2017,6 +2061,7 @@ static void generate_impl(wcb_handle* h, const float* mel, int B, const wcb_gen_
         stamp_reduce(h->stamp_base(buf, r), h->stamp_slots(), h->stamp_acc.as<unsigned long long>() + 2 * r, D.hs);
     }
     if (nb > 1) {   // best finished sequence of every utterance; its columns = the longest of them
+      bm.out_score = out_seq_scores;   // (nullable) that hypothesis's score, straight into the caller's [B]
       beam_output(bm, D.hs);
       HIPCHK(hipMemcpyAsync(out_ids, D.outbuf.p, (size_t)B * out_ld * 4, hipMemcpyDeviceToDevice, D.hs));
       if (cfg->async_out) {   // serving pipelines: every max_new column (pad past each best sequence), no
@@ -2035,6 +2080,8 @@ static void generate_impl(wcb_handle* h, const float* mel, int B, const wcb_gen_
       return;
     }
     HIPCHK(hipMemcpyAsync(out_ids, D.outbuf.p, (size_t)B * out_ld * 4, hipMemcpyDeviceToDevice, D.hs));
+    if (out_logprobs)
+      HIPCHK(hipMemcpyAsync(out_logprobs, D.lpbuf.p, (size_t)B * out_ld * 4, hipMemcpyDeviceToDevice, D.hs));
     HIPCHK(hipEventRecord(h->ev_dec[buf], D.hs));
     *out_steps = std::min(done, max_new);
     if (!cfg->async_out) {
@@ -2059,6 +2106,15 @@ int wcb_generate_biased(wcb_handle* h, const float* mel, int B, const wcb_gen_cf
   });
 }
 
+int wcb_generate_scored(wcb_handle* h, const float* mel, int B, const wcb_gen_cfg* cfg, const wcb_bias* bias,
+                        const wcb_bias_batch* bb, const int32_t* prefix, int prefix_len, int32_t* out_ids,
+                        float* out_logprobs, float* out_seq_scores, int32_t* out_steps, void* stream) {
+  return guarded(h, [&] {
+    REQUIRE(!(bias && bb), "wcb_generate_scored: a shared automaton or a bias batch, not both");
+    generate_impl(h, mel, B, cfg, bias, bb, prefix, prefix_len, out_ids, out_steps, stream, out_logprobs, out_seq_scores);
+  });
+}
+
 // ---- step-wise greedy decoding (SURVEY §8(b) wcb_decode_begin / wcb_decode_step): the decode step
 // of wcb_generate, one token per call, on the decode context kMaxCtx-1 (its own stream and buffers,
 // so generate() calls on contexts 0 .. nctx-1 are unaffected); eager launches (the caller inspects
@@ -2073,6 +2129,7 @@ struct wcb_state {
   BeamArgs bm;
   bool forest = false;   // per-utterance lists installed (wcb_decode_bias_batch): every step takes bias = NULL
   ForestDev fd;
+  bool logprobs = false; // wcb_decode_enable_logprobs: every step also writes its column of the context's lpbuf
 };
 
 // step-wise beam search: the beam path of wcb_generate one step per call (begin: cross-K/V of the
@@ -2239,6 +2296,7 @@ int wcb_decode_step(wcb_handle* h, wcb_state* st, const wcb_bias* bias, int32_t*
     } else {
       sc.score_out = scores;
       sc.embedded = true;   // (wcb_decode_begin embedded the first input; each finalize embeds the next)
+      if (st->logprobs) sc.logprob_out = D.lpbuf.as<float>();
     }
     if (st->forest) sc.forest = &st->fd;
     decode_step(h, sc);
@@ -2324,6 +2382,36 @@ int wcb_decode_result(wcb_handle* h, wcb_state* st, int32_t* out_ids, int out_ld
     if (n > 0)
       HIPCHK(hipMemcpy2DAsync(out_ids, (size_t)out_ld * 4, D.outbuf.p, (size_t)st->max_new * 4, (size_t)n * 4,
                               st->B, hipMemcpyDeviceToDevice, D.hs));
+    *out_steps = n;
+    sync_out(h, stream, D.hs);
+  });
+}
+
+int wcb_decode_enable_logprobs(wcb_handle* h, wcb_state* st) {
+  return guarded(h, [&] {
+    REQUIRE(h && st && st->h == h && h->step_state == st, "bad argument (state of this handle)");
+    if (st->nb > 1) throw WcbError(WCB_ERR_UNSUPPORTED, "token log-probs are greedy only (a beam-search state)");
+    if (st->fwd != 0) throw WcbError(WCB_ERR_STATE, "wcb_decode_enable_logprobs on a forward cache (wcb_forward_cached state)");
+    if (st->steps != 0) throw WcbError(WCB_ERR_STATE, "wcb_decode_enable_logprobs: after the first step (right after wcb_decode_begin)");
+    DecCtx& D = h->dc[wcb_handle::kMaxCtx - 1];
+    ensure_lp_ws(h, D, st->B, st->max_new);
+    HIPCHK(hipMemsetAsync(D.lpbuf.p, 0, (size_t)st->B * st->max_new * 4, D.hs));
+    st->logprobs = true;
+  });
+}
+
+int wcb_decode_logprobs(wcb_handle* h, wcb_state* st, float* out, int out_ld, int32_t* out_steps, void* stream) {
+  return guarded(h, [&] {
+    REQUIRE(h && st && st->h == h && h->step_state == st && out && out_steps, "bad argument");
+    if (!st->logprobs) throw WcbError(WCB_ERR_STATE, "wcb_decode_logprobs: log-probs are off (wcb_decode_enable_logprobs)");
+    const int n = st->steps;
+    REQUIRE(out_ld >= n && out_ld >= 1, "wcb_decode_logprobs: out_ld " + std::to_string(out_ld) + " < the " +
+                                            std::to_string(n) + " steps taken");
+    DecCtx& D = h->dc[wcb_handle::kMaxCtx - 1];
+    sync_in(h, stream, D.hs);
+    if (n > 0)
+      HIPCHK(hipMemcpy2DAsync(out, (size_t)out_ld * 4, D.lpbuf.p, (size_t)st->max_new * 4, (size_t)n * 4, st->B,
+                              hipMemcpyDeviceToDevice, D.hs));
     *out_steps = n;
     sync_out(h, stream, D.hs);
   });
@@ -2573,12 +2661,7 @@ void wcb_bias_destroy(wcb_bias* b) {
     } catch (...) {
     }
     for (DecCtx& D : h->dc)
-      if (D.gkey.find("/" + std::to_string(b->id) + "/") != std::string::npos) {
-        if (D.gexec) (void)hipGraphExecDestroy(D.gexec);
-        if (D.gexec_k) (void)hipGraphExecDestroy(D.gexec_k);
-        D.gexec = D.gexec_k = nullptr;
-        D.gkey.clear();
-      }
+      if ((D.gkey + D.gkey_lp).find("/" + std::to_string(b->id) + "/") != std::string::npos) D.drop_graphs();
     h->biases.erase(std::remove(h->biases.begin(), h->biases.end(), b), h->biases.end());
   }
   for (DevBuf* x : {&b->root_bits, &b->root_child, &b->trans_off, &b->trans_tok, &b->trans_dst, &b->st_depth, &b->st_keep})
@@ -2644,7 +2727,8 @@ int wcb_debug_copy(wcb_handle* h, const char* name, void* dst, int64_t bytes, in
     const std::map<std::string, DevBuf*> bufs = {{"xt", &h->xt}, {"hbuf", &h->hbuf}, {"x", &h->x}, {"h", &h->h},
                                                  {"qkv", &h->qkv}, {"att", &h->att}, {"ffn", &h->ffn},
                                                  {"encout", &h->encout}, {"xkv", &h->xkv2[0]},
-                                                 {"logits", &h->dc[0].logits}};
+                                                 {"logits", &h->dc[0].logits},
+                                                 {"step_logits", &h->dc[wcb_handle::kMaxCtx - 1].logits}};
     if (bytes == 0) return;   // only set the layer limit
     REQUIRE(dst, "null dst");
     auto it = bufs.find(name);
@@ -2778,6 +2862,46 @@ int wcb_op_gemm_ln(int dtype, const float* X, const float* ln_w, const float* ln
     g.bias = bias; g.act = act; g.out_f32 = out_f32;
     gemm(DType(dtype), g, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
+  });
+}
+
+int wcb_op_lm_head_lse(int dtype, const void* A, const void* W, int M, int V, int K, int walkers, float* logits, long ld,
+                       float* lse, int32_t* argmax, void* stream) {
+  return guarded(nullptr, [&] {
+    REQUIRE(A && W && logits && lse && argmax && M > 0 && M <= 64 && V > 0 && K > 0 && ld >= V,
+            "bad argument (1 <= M <= 64, ld >= V, every pointer)");
+    REQUIRE(dtype >= WCB_BF16 && dtype <= WCB_F32, "dtype");
+    REQUIRE(walkers >= 0 && walkers <= 4096, "walkers: 0 (default) .. 4096");
+    const DType dt = DType(dtype);
+    // the widths the decode step's LM head runs at: the decode GEMM's column walk, or the older skinny kernel
+    if (!gemm_dec_supported(dt, K) && K != 32 && K != 2560)
+      throw WcbError(WCB_ERR_UNSUPPORTED, "K: 64, 128, 256, 384, 512, 768, 1024, 1280 (column walk) or 32, 2560 (skinny kernel)");
+    hipStream_t st = (hipStream_t)stream;
+    const int wk = walkers > 0 ? walkers : kDecWalkers;
+    const int nchunk = lm_head_partials(dt, K, V, wk);
+    struct Scratch { DevBuf b; ~Scratch() { b.release(); } } pv, pi, pm, ps, zero, wpad, wfm;
+    const size_t np = (size_t)M * nchunk * 4;
+    pv.b.ensure(np); pi.b.ensure(np); pm.b.ensure(np); ps.b.ensure(np); zero.b.ensure(16);
+    GemmArgs lm = drow(A, K, W, M, V, K, logits, ld);
+    lm.out_f32 = 1;
+    lm.walkers = wk;
+    lm.sel_val = pv.b.as<float>(); lm.sel_idx = pi.b.as<int>();
+    lm.sel_max = pm.b.as<float>(); lm.sel_sum = ps.b.as<float>();
+    lm.sel_step = zero.b.as<int>();   // step 0 against min_new 0: no EOS mask; lam 0: no boost
+    int nw = 0, kpw = 0;
+    if (dt != kF32 && gemm_dec_supported(dt, K) && lean_cfg(K, nw, kpw)) {
+      // as the runtime's token embedding: a fragment-major copy of whole 16-row tiles, zero rows past V
+      const size_t e = esize(dtype), vp = (size_t)(V + 15) / 16 * 16;
+      wpad.b.ensure(vp * K * e);
+      wfm.b.ensure(vp * K * e);
+      HIPCHK(hipMemcpyAsync(wpad.b.p, W, (size_t)V * K * e, hipMemcpyDeviceToDevice, st));
+      frag_major(dt, wpad.b.p, (int)vp, K, nw, kpw, wfm.b.p, st);
+      lm.W_fm = wfm.b.p;
+    }
+    gemm(dt, lm, st);
+    lm_head_lse_finalize(lm.sel_val, lm.sel_idx, lm.sel_max, lm.sel_sum, M, nchunk, lse, argmax, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));   // the scratch buffers are freed on return
   });
 }
 

@@ -45,6 +45,13 @@ def _stream(device) -> int:
 @dataclass
 class GenerateOutput:
     sequences: torch.Tensor
+    # generate(output_logprobs=True). Greedy: token_logprobs [B, n] f32, the model's own log-prob of every
+    # generated token (raw logits: no boost, no EOS mask; 0 where a finished row emits pad), aligned with
+    # sequences[:, len(prefix):], and avg_logprob [B], its mean over each row's tokens up to and including its
+    # EOS (Whisper's avg_logprob). Beam search: sequences_scores [B] f32 (HF's).
+    token_logprobs: Optional[torch.Tensor] = None
+    avg_logprob: Optional[torch.Tensor] = None
+    sequences_scores: Optional[torch.Tensor] = None
 
 
 @dataclass
@@ -171,6 +178,17 @@ class StepDecoder:
         if max_new is not None and max_new < n.value:
             raise ValueError(f"result(max_new={max_new}): {n.value} columns were generated")
         return m._whisper_trim(out[:, :n.value].to(torch.int64))
+
+    def logprobs(self):
+        """[B, steps] f32: the model's own log-prob of the token each step chose (decode_begin(logprobs=True);
+        greedy), 0 where a finished row emitted pad."""
+        m = self.model
+        width = self.info()[0]
+        out = torch.empty(self.B, width, dtype=torch.float32, device=m.device)
+        n = C.c_int32(0)
+        _lib.check(m._lib.wcb_decode_logprobs(m._h, self._st, _ptr(out), width, C.byref(n), _stream(m.device)), m._h,
+                   "wcb_decode_logprobs")
+        return out[:, :n.value]
 
     def close(self):
         if self._st:
@@ -460,7 +478,7 @@ class WhisperCB:
                  num_beams: Optional[int] = None, bias_list=None, bias_boost: float = 0.0,
                  min_new_tokens: int = 0, prompt_ids=None, return_dict_in_generate: bool = False,
                  generation_config=None, use_graph: bool = True, block: bool = True, bias_lists=None,
-                 per_utterance_bias: bool = False, **kwargs):
+                 per_utterance_bias: bool = False, output_logprobs: bool = False, **kwargs):
         """Greedy (num_beams = 1, the reference's eval setting) or HF beam
         search (num_beams = 2..8, [tf] generation/utils.py:3208) on the device.
 
@@ -481,9 +499,19 @@ class WhisperCB:
         must be kept alive and are valid only after `synchronize()`. Only meaningful with
         `min_new_tokens >= max_length` (no early-exit polling). Beam search returns all `max_length`
         columns then (pad past each clip's best sequence: its length is not read back).
+
+        `output_logprobs=True` (implies `return_dict_in_generate`) also returns, computed on the device in
+        the same decode (wcb_generate_scored): greedy, `token_logprobs` [B, n] — the model's own log-prob of
+        every generated token from the raw logits (the boost and the EOS mask pick the token but never enter
+        it), 0 where a finished row emits pad — and `avg_logprob` [B]; beam search, `sequences_scores` [B].
+        With `block=False` the result is a GenerateOutput of device views valid after `synchronize()`:
+        `sequences` the int32 generated columns, `token_logprobs` / `sequences_scores`; `avg_logprob` is a
+        host computation and stays None.
         """
         if not self._loaded:
             raise _lib.WcbError("weights not loaded")
+        if output_logprobs:
+            return_dict_in_generate = True
         x_all = self._features(input_features)
         if bias_lists is None and per_utterance_bias and bias_list is None and bias_boost > 0 and bias_spans is not None:
             bias_lists = self._spans_to_lists(bias_spans)
@@ -498,7 +526,8 @@ class WhisperCB:
             kw = dict(labels=labels, bias_spans=bias_spans, max_length=max_length, num_beams=num_beams,
                       bias_list=bias_list, bias_boost=bias_boost, min_new_tokens=min_new_tokens,
                       prompt_ids=prompt_ids, return_dict_in_generate=return_dict_in_generate,
-                      generation_config=generation_config, use_graph=use_graph, block=True)
+                      generation_config=generation_config, use_graph=use_graph, block=True,
+                      output_logprobs=output_logprobs)
             if bias_lists is None and bias_list is None and bias_boost > 0 and bias_spans is not None:
                 kw["bias_list"], kw["bias_spans"] = self._spans_to_phrases(bias_spans), None
             parts = [self.generate(x_all[i:i + per_call],
@@ -508,6 +537,17 @@ class WhisperCB:
             Wd = max(t.shape[1] for t in seqs)
             fill = self.dims.pad_token_id
             out = torch.cat([torch.nn.functional.pad(t, (0, Wd - t.shape[1]), value=fill) for t in seqs])
+            if output_logprobs:   # the parts' scores joined; log-prob columns past a part's width are 0
+                def join(name, width=None):
+                    vals = [getattr(p, name) for p in parts]
+                    if any(v is None for v in vals):
+                        return None
+                    if width is not None:
+                        vals = [torch.nn.functional.pad(v, (0, width - v.shape[1])) for v in vals]
+                    return torch.cat(vals)
+                lp_w = max((p.token_logprobs.shape[1] for p in parts if p.token_logprobs is not None), default=0)
+                return GenerateOutput(sequences=out, token_logprobs=join("token_logprobs", lp_w),
+                                      avg_logprob=join("avg_logprob"), sequences_scores=join("sequences_scores"))
             return GenerateOutput(sequences=out) if return_dict_in_generate else out
         gc = generation_config or self.generation_config
         max_length = int(max_length if max_length is not None else getattr(gc, "max_length", 448))
@@ -536,6 +576,8 @@ class WhisperCB:
         out = torch.empty(B, max_new, dtype=torch.int32, device=self.device)
         steps = C.c_int32(0)
         pre = np.asarray(prefix, dtype=np.int32)
+        if output_logprobs:
+            return self._generate_scored(x, cfg, bl, bias_lists if bias_boost > 0 else None, prefix, pre, out, block)
         if bias_lists is not None and bias_boost > 0:
             bb = BiasBatch(self, bias_lists)   # per call: not in the automaton LRU
             try:
@@ -558,15 +600,54 @@ class WhisperCB:
             return GenerateOutput(sequences=torch.cat([sot, ids], dim=1))
         return self._whisper_trim(ids)
 
+    def _generate_scored(self, x, cfg, bl, bias_lists, prefix, pre, out, block) -> GenerateOutput:
+        """generate(output_logprobs=True) on one library call: wcb_generate_scored with the shared automaton
+        `bl`, the per-clip `bias_lists`, or neither."""
+        B, max_new, beams = x.shape[0], cfg.max_new_tokens, cfg.num_beams > 1
+        lp = None if beams else torch.zeros(B, max_new, dtype=torch.float32, device=self.device)
+        ss = torch.zeros(B, dtype=torch.float32, device=self.device) if beams else None
+        steps = C.c_int32(0)
+        bb = BiasBatch(self, bias_lists) if bias_lists is not None else None   # per call: not in the automaton LRU
+        try:
+            _lib.check(self._lib.wcb_generate_scored(self._h, _ptr(x), B, C.byref(cfg), bl._h if (bl and not bb) else None,
+                                                     bb._h if bb else None,
+                                                     pre.ctypes.data if len(prefix) > 1 else None, len(prefix),
+                                                     _ptr(out), _ptr(lp) if lp is not None else None,
+                                                     _ptr(ss) if ss is not None else None, C.byref(steps),
+                                                     _stream(self.device)), self._h, "wcb_generate_scored")
+        finally:
+            if bb:
+                bb.close()   # the call copied it (also with block=False)
+        n = steps.value
+        if not block:   # device views, valid after synchronize()
+            return GenerateOutput(sequences=out[:, :n], token_logprobs=lp[:, :n] if lp is not None else None,
+                                  sequences_scores=ss)
+        ids = out[:, :n].to(torch.int64)
+        sot = torch.tensor(prefix, dtype=torch.int64, device=self.device)[None].expand(B, -1)
+        res = GenerateOutput(sequences=torch.cat([sot, ids], dim=1), sequences_scores=ss)
+        if lp is not None:
+            res.token_logprobs = lp[:, :n]
+            # Whisper's avg_logprob on the host: each row's tokens up to and including its EOS (a finished row's
+            # pads, which may equal EOS, come after it), every token of a row that never finished
+            ids_h, lp_h = ids.cpu().numpy(), res.token_logprobs.cpu().numpy()
+            avg = np.zeros(B, dtype=np.float32)
+            for b in range(B):
+                hit = np.flatnonzero(ids_h[b] == self.dims.eos_token_id)
+                cnt = int(hit[0]) + 1 if len(hit) else n
+                avg[b] = lp_h[b, :cnt].astype(np.float64).mean() if cnt else 0.0
+            res.avg_logprob = torch.from_numpy(avg).to(self.device)
+        return res
+
     def decode_begin(self, encoder_outputs, prompt_ids=None, bias_list=None, bias_boost: float = 0.0,
                      min_new_tokens: int = 0, num_beams: int = 1, max_length: Optional[int] = None,
-                     bias_lists=None) -> "StepDecoder":
+                     bias_lists=None, logprobs: bool = False) -> "StepDecoder":
         """Step-wise decoding from an encoder output [B, 1500, d] (this model's dtype, on its device): the
         streaming form of generate() (wcb_decode_begin / wcb_decode_begin_beams). Greedy (num_beams = 1) or
         beam search (num_beams 2..8; `max_length` = generate()'s, the beams' length cap: None = the
         max_target_positions cap). `prompt_ids` = one prompt for every clip or a [B, P] array of per-clip
         prompts (decoder_start_token_id is appended as generate() does). `bias_lists` = per-clip phrase lists as
-        generate() takes them (wcb_decode_bias_batch; a shared `bias_list` of phrases is appended to each)."""
+        generate() takes them (wcb_decode_bias_batch; a shared `bias_list` of phrases is appended to each).
+        `logprobs=True` (greedy): StepDecoder.logprobs() gives the token log-probs of the steps taken."""
         enc = self._encoder_state(encoder_outputs)   # [B, 1500, d] checked: the library copies B·1500·d
         B = enc.shape[0]
         if B > 64:
@@ -600,6 +681,8 @@ class WhisperCB:
                                                   int(min_new_tokens), C.byref(st), _stream(self.device)), self._h,
                        "wcb_decode_begin")
         dec = StepDecoder(self, st, B, bl, nb)
+        if logprobs:   # greedy only (wcb.h): every step records the log-prob of its token
+            _lib.check(self._lib.wcb_decode_enable_logprobs(self._h, st), self._h, "wcb_decode_enable_logprobs")
         if bias_lists is not None and bias_boost > 0:
             bb = BiasBatch(self, bias_lists)
             try:
