@@ -300,6 +300,40 @@ int wcb_decode_enable_logprobs(wcb_handle* h, wcb_state* st);
  * far, *out_steps (host) = n; out_ld < n is WCB_ERR_ARG; log-probs not enabled: WCB_ERR_STATE. */
 int wcb_decode_logprobs(wcb_handle* h, wcb_state* st, float* out, int out_ld, int32_t* out_steps, void* stream);
 
+/* Temperature sampling (greedy decodes): the token of a step is drawn from softmax(score / T), score = logit +
+ * bias boost (a masked EOS stays excluded), as a perturbed argmax — Gumbel-max — inside the kernels that take
+ * the argmax today, with no logits leaving the chip:
+ *   x[v] = fmaf(score[v], 1.0f / T, g(seed, t, v)),  token = argmax_v x[v] (lowest index on ties)
+ *   g(seed, t, v) = -logf(-logf(u)),  u = ((r >> 9) + 0.5f) * 2^-23 (exact in f32, 0 < u < 1),
+ *   r = philox4x32_10(counter (v >> 2, t, 0, 0), key (lo32(seed), hi32(seed)))[v & 3]
+ * with seed the clip's 64-bit seed and t the 0-based index of the generated token (csrc/sample.h holds the one
+ * definition the kernels and wcb_sample_noise compile). A decode is a pure function of (inputs, seeds, T): the
+ * same seeds give the same tokens, in generate and step-wise, eager and graph replay, whatever the batch split.
+ * Token log-probs keep their meaning (raw logit - logsumexp of the raw logits: untempered, no boost). Step-wise,
+ * wcb_decode_step's `scores` holds the winner's perturbed value x (not its boosted logit). Seeds and 1/T are
+ * copied on the decode stream into a buffer of the decode context (the host array may be freed on return,
+ * async_out = 1 and several decode contexts in flight included); a sampled decode replays a captured graph of
+ * its own, kept beside the unscored and scored ones, whose key never contains the seeds or the temperature.
+ * With sampling off every existing path launches exactly the kernels, arguments and graphs it launched before.
+ * Errors: temperature <= 0 or not finite, NULL seeds: WCB_ERR_ARG; num_beams > 1 / a beam-search state:
+ * WCB_ERR_UNSUPPORTED; both bias and bb: WCB_ERR_ARG. */
+typedef struct { float temperature;        /* > 0 */
+                 const uint64_t* seeds;    /* HOST [B], one per clip */ } wcb_sample_cfg;
+
+/* wcb_generate_scored's greedy form with sampling; out_logprobs may be NULL */
+int wcb_generate_sampled(wcb_handle*, const float* mel, int B, const wcb_gen_cfg*, const wcb_sample_cfg*,
+                         const wcb_bias*, const wcb_bias_batch*, const int32_t* prefix, int prefix_len,
+                         int32_t* out_ids, float* out_logprobs, int32_t* out_steps, void* stream);
+/* after wcb_decode_begin, before the first step, greedy state only (beam state: WCB_ERR_UNSUPPORTED;
+   after a step or on a forward cache: WCB_ERR_STATE); seeds HOST [B] */
+int wcb_decode_enable_sampling(wcb_handle*, wcb_state*, float temperature, const uint64_t* seeds);
+/* wcb_op_lm_head_lse with the perturbed argmax: seeds HOST [M]; sampled[M] int32 DEVICE */
+int wcb_op_lm_head_sample(int dtype, const void* A, const void* W, int M, int V, int K, int walkers,
+                          float temperature, const uint64_t* seeds, int step, float* logits, long ld,
+                          float* lse, int32_t* sampled, void* stream);
+/* HOST, no GPU: out[i] = g(seed, step, v0 + i), the same inline function the kernels compile */
+int wcb_sample_noise(uint64_t seed, int step, int v0, int n, float* out);
+
 /* debug counters by name (not part of wcb_profile_read): "graph_captures" = decode graphs instantiated so
  * far on this handle. Unknown name: WCB_ERR_ARG. */
 int wcb_debug_counter(const wcb_handle* h, const char* name, int64_t* out);

@@ -28,6 +28,10 @@ class WcbGenCfg(C.Structure):
                 ("bias_boost", C.c_float), ("use_graph", C.c_int), ("async_out", C.c_int)]
 
 
+class WcbSampleCfg(C.Structure):
+    _fields_ = [("temperature", C.c_float), ("seeds", C.POINTER(C.c_uint64))]
+
+
 class WcbTensorView(C.Structure):
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("dtype", C.c_int), ("ndim", C.c_int),
                 ("shape", C.c_int64 * 4), ("stride", C.c_int64 * 4)]
@@ -72,6 +76,12 @@ SIGNATURES = {
     "wcb_decode_enable_logprobs": (C.c_int, [_P, _P]),
     "wcb_decode_logprobs": (C.c_int, [_P, _P, _P, C.c_int, C.POINTER(C.c_int32), _P]),
     "wcb_op_lm_head_lse": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_long, _P, _P, _P]),
+    "wcb_generate_sampled": (C.c_int, [_P, _P, C.c_int, C.POINTER(WcbGenCfg), C.POINTER(WcbSampleCfg), _P, _P, _P, C.c_int,
+                                       _P, _P, C.POINTER(C.c_int32), _P]),
+    "wcb_decode_enable_sampling": (C.c_int, [_P, _P, C.c_float, C.POINTER(C.c_uint64)]),
+    "wcb_op_lm_head_sample": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                        C.POINTER(C.c_uint64), C.c_int, _P, C.c_long, _P, _P, _P]),
+    "wcb_sample_noise": (C.c_int, [C.c_uint64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]),
     "wcb_debug_counter": (C.c_int, [_P, C.c_char_p, C.POINTER(C.c_int64)]),
     "wcb_debug_copy": (C.c_int, [_P, C.c_char_p, _P, C.c_int64, C.c_int]),
     "wcb_profile_enable": (C.c_int, [_P, C.c_int]),

@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "kernels.h"
+#include "sample.h"
 
 typedef uint16_t bf16_t;
 typedef _Float16 f16_t;

@@ -916,7 +916,9 @@ static bool launch_pp(const GemmArgs& g, hipStream_t s) {
 //  * st_out: a residual-writing GEMM (NF = 1) publishes those partial sums of the new x rows.
 //  * sel_val: the LM head reduces its logits tile to a per-row (max, argmax) partial with the
 //    bias-list root boost and the EOS mask applied (k_select.hip finishes the reduction).
-template <typename T, int MF, int NF, int NW, int KS, bool LN>
+//  * SAMPLE (the LM head with g.sel_seeds): the partial compares the perturbed scores of sample.h; a
+//    compile-time variant, so the greedy instantiations keep their code.
+template <typename T, int MF, int NF, int NW, int KS, bool LN, bool SAMPLE = false>
 __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(GemmArgs g) {
   using Frag = typename DT<T>::frag;
   constexpr int NT = NW * 64, BNC = NF * 16;
@@ -1061,6 +1063,9 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(GemmArgs g) {
     __syncthreads();
   }
   const bool mask_eos = g.sel_val && *g.sel_step < g.sel_min_new;
+  [[maybe_unused]] int smp_step = 0;
+  [[maybe_unused]] float smp_inv_t = 1.f;
+  if constexpr (SAMPLE) { smp_step = *g.sel_step; smp_inv_t = *g.sel_inv_t; }
   // epilogue: thread → (row, col) with the columns of a row contiguous in the wave, so row-wise
   // reductions (stats partials: 16 lanes; argmax partial: BNC lanes) are shuffles
 #pragma unroll
@@ -1109,6 +1114,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(GemmArgs g) {
         x = v;
         if (g.sel_lam != 0.f)
           x = bias_bonus(x, g.sel_lam, g.sel_rowbase[row] + (int)((g.sel_root_bits[nn >> 5] >> (nn & 31)) & 1u));
+        if constexpr (SAMPLE) x = sample_perturb(x, smp_inv_t, sample_noise(g.sel_seeds[row], smp_step, nn));
         if (mask_eos && nn == g.sel_eos) x = -INFINITY;
         xi = nn;
       }
@@ -1160,7 +1166,12 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(GemmArgs g) {
 //    one (row, column) output: bias, GELU, residual, f32 / T / x16 stores, KV-cache append (mode 2),
 //    per-16-column LN partial sums (st_out, the older skinny consumers) and the LM head's argmax
 //    partial (sel_val: per workgroup and row, the running best over the tiles it walks).
-template <typename T, int MF, int NW, int KPW, int AM, bool P, bool WFM = false>
+//  * SAMPLE (the LM head with g.sel_seeds, P only): the argmax partial compares the perturbed scores of
+//    sample.h — one Philox block and two logf per output, computed per lane: a row's 16 columns sit on 16
+//    lanes with one or two outputs per thread at every d_model (EP), so sharing a block over its 4 columns
+//    would leave the wave issuing the same instructions. A compile-time variant: the greedy instantiations
+//    keep their code.
+template <typename T, int MF, int NW, int KPW, int AM, bool P, bool WFM = false, bool SAMPLE = false>
 __global__ __launch_bounds__(NW * 64) void gemm_dec_kernel(GemmArgs g) {
   using Frag = typename DT<T>::frag;
   constexpr int NT = NW * 64, K = NW * KPW * 32, R = MF * 16;
@@ -1235,6 +1246,9 @@ __global__ __launch_bounds__(NW * 64) void gemm_dec_kernel(GemmArgs g) {
   }
   float pf_bias[EP], pf_res[EP];   // epilogue operands of this thread's outputs (single-tile launches)
   int pf_rb[EP];                   // bias-boost base units of this thread's rows (LM head)
+  [[maybe_unused]] uint64_t pf_seed[SAMPLE ? EP : 1];   // sampling seeds of this thread's rows
+  [[maybe_unused]] int smp_step = 0;
+  [[maybe_unused]] float smp_inv_t = 1.f;
 #pragma unroll
   for (int it = 0; it < EP; ++it) {
     const int o = it * NT + tid;
@@ -1243,7 +1257,9 @@ __global__ __launch_bounds__(NW * 64) void gemm_dec_kernel(GemmArgs g) {
     pf_bias[it] = (ok && g.bias) ? g.bias[nn] : 0.f;
     pf_res[it] = (ok && g.resid && !(g.mode == 2 && nn >= g.n_split)) ? g.resid[c_row(g, row) + nn] : 0.f;
     pf_rb[it] = (g.sel_val && g.sel_lam != 0.f && o < R * 16 && row < g.M) ? g.sel_rowbase[row] : 0;
+    if constexpr (SAMPLE) pf_seed[it] = g.sel_seeds[min(row, g.M - 1)];
   }
+  if constexpr (SAMPLE) { smp_step = *g.sel_step; smp_inv_t = *g.sel_inv_t; }
   __builtin_amdgcn_sched_barrier(0);
   // ---------------- LayerNorm of the A rows: statistics from the loaded values, parameters via LDS
   if constexpr (LN) {
@@ -1403,6 +1419,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_dec_kernel(GemmArgs g) {
           x = v;
           if (g.sel_lam != 0.f)
             x = bias_bonus(x, g.sel_lam, pf_rb[it] + (int)((rbw >> (nn & 31)) & 1u));
+          if constexpr (SAMPLE) x = sample_perturb(x, smp_inv_t, sample_noise(pf_seed[it], smp_step, nn));
           if (mask_eos && nn == g.sel_eos) x = -INFINITY;
           xi = nn;
         }
@@ -2324,6 +2341,11 @@ static void launch_dec_k(const GemmArgs& g, hipStream_t s) {
   } else {   // the LM head: kDecWalkers column walkers per row block (= argmax partials per row)
     const int gx = std::min(ntile, g.walkers > 0 ? g.walkers : kDecWalkers);
     int nw = 0, kpw = 0;
+    // temperature sampling (g.sel_seeds): the same launches on the sampled instantiations, built for the
+    // LM head's widths (K <= 1280: every d_model) and A modes
+    constexpr bool kSampled = AM != 3 && NW * KPW * 32 <= 1280;
+    const bool sample = g.sel_val && g.sel_seeds;
+    if (sample && !kSampled) throw std::runtime_error("internal error: sampled LM head on a launch without a sampled kernel");
     if constexpr (sizeof(T) == 2 && AM != 3) {
       // the copy's split matches; it covers whole 16-column tiles (the LM head's rows are padded with zeros)
       if (g.W_fm && lean_cfg(g.K, nw, kpw) && nw == NW && kpw == KPW) {
@@ -2333,10 +2355,28 @@ static void launch_dec_k(const GemmArgs& g, hipStream_t s) {
           GemmArgs h = g;
           h.A = g.ln_scratch; h.lda = g.K;
           h.ln_w = h.ln_b = nullptr; h.ln_a16 = nullptr; h.st_in = nullptr;
+          if constexpr (kSampled) {
+            if (sample) {
+              WCB_LAUNCH((gemm_dec_kernel<T, MF, NW, KPW, 0, true, true, true>), dim3(gx, gy), dim3(NW * 64), 0, s, h);
+              return;
+            }
+          }
           WCB_LAUNCH((gemm_dec_kernel<T, MF, NW, KPW, 0, true, true>), dim3(gx, gy), dim3(NW * 64), 0, s, h);
           return;
         }
+        if constexpr (kSampled) {
+          if (sample) {
+            WCB_LAUNCH((gemm_dec_kernel<T, MF, NW, KPW, AM, true, true, true>), dim3(gx, gy), dim3(NW * 64), 0, s, g);
+            return;
+          }
+        }
         WCB_LAUNCH((gemm_dec_kernel<T, MF, NW, KPW, AM, true, true>), dim3(gx, gy), dim3(NW * 64), 0, s, g);
+        return;
+      }
+    }
+    if constexpr (kSampled) {
+      if (sample) {
+        WCB_LAUNCH((gemm_dec_kernel<T, MF, NW, KPW, AM, true, false, true>), dim3(gx, gy), dim3(NW * 64), 0, s, g);
         return;
       }
     }
@@ -2418,6 +2458,19 @@ static void launch_tile(const GemmArgs& g, hipStream_t s) {
 template <typename T, int MF, int NF, int NW, int KS>
 static void launch_skinny_k(const GemmArgs& g, hipStream_t s) {
   const dim3 grid((g.N + NF * 16 - 1) / (NF * 16), (g.M + MF * 16 - 1) / (MF * 16));
+  // the LM head's 64-column form at the widths the decode GEMM's table leaves to it, <= 64 rows: its
+  // sampled instantiations (g.sel_seeds)
+  constexpr int K = NW * KS * 32;
+  constexpr bool kSampled = NF == 4 && MF <= 2 && (K == 32 || K == 2560 || K == 6144);
+  if (g.sel_val && g.sel_seeds && !kSampled)
+    throw std::runtime_error("internal error: sampled LM head on a launch without a sampled kernel");
+  if constexpr (kSampled) {
+    if (g.sel_val && g.sel_seeds) {
+      if (g.ln_w) WCB_LAUNCH((gemm_skinny_kernel<T, MF, NF, NW, KS, true, true>), grid, dim3(NW * 64), 0, s, g);
+      else WCB_LAUNCH((gemm_skinny_kernel<T, MF, NF, NW, KS, false, true>), grid, dim3(NW * 64), 0, s, g);
+      return;
+    }
+  }
   if (g.ln_w) WCB_LAUNCH((gemm_skinny_kernel<T, MF, NF, NW, KS, true>), grid, dim3(NW * 64), 0, s, g);
   else WCB_LAUNCH((gemm_skinny_kernel<T, MF, NF, NW, KS, false>), grid, dim3(NW * 64), 0, s, g);
 }
@@ -2436,6 +2489,8 @@ static bool launch_skinny_mf(const GemmArgs& g, hipStream_t s) {
 
 template <typename T>
 static void gemm_t(const GemmArgs& g, hipStream_t s) {
+  if (g.sel_seeds && (!g.sel_val || g.tile || g.M > 64))
+    throw std::runtime_error("internal error: sampling on a launch that is not the greedy LM head");
   if (g.tile) {   // decoder rows > 64 (beams, prefill): MFMA tiles, each weight tile read once per 64-128 rows
     if constexpr (sizeof(T) == 2) {
       // tile 2 (192+ rows, the d-wide and wide projections): 64-row tiles over a deep LDS-DMA ring, so

@@ -21,6 +21,12 @@
 // vocabulary-pass copy of a root child is one lam short (never above its exact value), and a token in
 // both lists keeps the larger candidate, the trans value (never below k - d + 1). delta(s, v) looks in
 // trans(s), then in the clip's list, then falls back to the clip's root.
+//
+// Temperature sampling (SAMPLE instantiations, SelectArgs::seeds; sample.h): every comparison above is made
+// on x[v] = sample_perturb(score[v], 1/T, g(seed of the row, step, v)) instead of score[v], so the chosen
+// token is a draw from softmax(score / T) (Gumbel-max). The finalize stays exact by the same argument: both
+// copies of a token carry the same noise g and x is monotone in score, so an underestimated copy never wins;
+// a masked EOS stays -inf. The log-prob of the chosen token is still its raw logit − logsumexp(raw logits).
 #include <algorithm>
 
 #include "common.h"
@@ -43,6 +49,7 @@ WCB_DEV void merge_lse_partials(const float* pm, const float* ps, int n, int lan
   }
 }
 
+template <bool SAMPLE>
 __global__ __launch_bounds__(256) void select_partial_kernel(SelectArgs a) {
   const int m = blockIdx.y, c = blockIdx.x;
   const int chunk = (a.V + a.nchunk - 1) / a.nchunk;
@@ -50,11 +57,15 @@ __global__ __launch_bounds__(256) void select_partial_kernel(SelectArgs a) {
   const float* row = a.logits + (long)m * a.ld;
   const bool mask_eos = *a.step < a.min_new;
   const int rb = a.rowbase[m];
+  [[maybe_unused]] const int step = SAMPLE ? *a.step : 0;
+  [[maybe_unused]] const float inv_t = SAMPLE ? *a.inv_t : 1.f;
+  [[maybe_unused]] const uint64_t seed = SAMPLE ? a.seeds[m] : 0ull;
   float bv = -INFINITY;
   int bi = 0x7fffffff;
   for (int v = v0 + threadIdx.x; v < v1; v += 256) {
     float x = row[v];
     if (a.lam != 0.f) x = bias_bonus(x, a.lam, rb + (int)((a.root_bits[v >> 5] >> (v & 31)) & 1u));
+    if constexpr (SAMPLE) x = sample_perturb(x, inv_t, sample_noise(seed, step, v));
     if (mask_eos && v == a.eos) x = -INFINITY;
     if (better(x, v, bv, bi)) { bv = x; bi = v; }
   }
@@ -82,7 +93,7 @@ __global__ __launch_bounds__(256) void select_partial_kernel(SelectArgs a) {
 // One wave per row; the last row to finish (atomic ticket) advances the step/position counters.
 // EMB: the row's next-step input embedding in the same launch (k_norm.hip embed_kernel's arithmetic and
 // stats grouping, 64 columns per pass).
-template <typename T, bool EMB, bool FOREST>
+template <typename T, bool EMB, bool FOREST, bool SAMPLE = false>
 __global__ __launch_bounds__(64) void select_finalize_kernel(SelectArgs a) {
   const int m = blockIdx.x, lane = threadIdx.x;
   const int step = *a.step;
@@ -103,10 +114,13 @@ __global__ __launch_bounds__(64) void select_finalize_kernel(SelectArgs a) {
   if (a.lam != 0.f) {
     const float* row = a.logits + (long)m * a.ld;
     const int d = a.st_depth[s], k = a.st_keep[s];
+    [[maybe_unused]] const float inv_t = SAMPLE ? *a.inv_t : 1.f;
+    [[maybe_unused]] const uint64_t seed = SAMPLE ? a.seeds[m] : 0ull;
     for (int t = t0 + lane; t < t1; t += 64) {
       const int v = a.trans_tok[t];
       const int d2 = a.st_depth[a.trans_dst[t]];
       float x = bias_bonus(row[v], a.lam, d2 - d + min(k, d + 1 - d2));
+      if constexpr (SAMPLE) x = sample_perturb(x, inv_t, sample_noise(seed, step, v));
       if (mask_eos && v == a.eos) x = -INFINITY;
       if (better(x, v, bv, bi)) { bv = x; bi = v; }
     }
@@ -114,6 +128,7 @@ __global__ __launch_bounds__(64) void select_finalize_kernel(SelectArgs a) {
       for (int t = a.forest.rc_off[m] + lane; t < a.forest.rc_off[m + 1]; t += 64) {
         const int v = a.forest.rc_tok[t];
         float x = bias_bonus(row[v], a.lam, k - d + 1);
+        if constexpr (SAMPLE) x = sample_perturb(x, inv_t, sample_noise(seed, step, v));
         if (mask_eos && v == a.eos) x = -INFINITY;
         if (better(x, v, bv, bi)) { bv = x; bi = v; }
       }
@@ -261,21 +276,27 @@ void write_i32(int* dst, const int* host_src, int n, hipStream_t s) {
   }
 }
 
-template <bool FOREST>
+template <bool FOREST, bool SAMPLE>
 static void select_finalize_launch(const SelectArgs& a, hipStream_t s) {
   if (!a.emb) {
-    WCB_LAUNCH((select_finalize_kernel<float, false, FOREST>), dim3(a.M), dim3(64), 0, s, a);
+    WCB_LAUNCH((select_finalize_kernel<float, false, FOREST, SAMPLE>), dim3(a.M), dim3(64), 0, s, a);
   } else if (a.dtype == kBF16) {
-    WCB_LAUNCH((select_finalize_kernel<bf16_t, true, FOREST>), dim3(a.M), dim3(64), 0, s, a);
+    WCB_LAUNCH((select_finalize_kernel<bf16_t, true, FOREST, SAMPLE>), dim3(a.M), dim3(64), 0, s, a);
   } else if (a.dtype == kF16) {
-    WCB_LAUNCH((select_finalize_kernel<f16_t, true, FOREST>), dim3(a.M), dim3(64), 0, s, a);
+    WCB_LAUNCH((select_finalize_kernel<f16_t, true, FOREST, SAMPLE>), dim3(a.M), dim3(64), 0, s, a);
   } else {
-    WCB_LAUNCH((select_finalize_kernel<float, true, FOREST>), dim3(a.M), dim3(64), 0, s, a);
+    WCB_LAUNCH((select_finalize_kernel<float, true, FOREST, SAMPLE>), dim3(a.M), dim3(64), 0, s, a);
   }
 }
 void select_finalize(const SelectArgs& a, hipStream_t s) {
-  if (a.forest.root) select_finalize_launch<true>(a, s);
-  else select_finalize_launch<false>(a, s);
+  if (a.seeds) {   // temperature sampling: the sampled instantiations
+    if (a.forest.root) select_finalize_launch<true, true>(a, s);
+    else select_finalize_launch<false, true>(a, s);
+  } else if (a.forest.root) {
+    select_finalize_launch<true, false>(a, s);
+  } else {
+    select_finalize_launch<false, false>(a, s);
+  }
 }
 
 // decode start with per-utterance lists: every row in its clip's root state (the zero fill means "state 0",
@@ -321,7 +342,8 @@ void lm_head_lse_finalize(const float* part_val, const int* part_idx, const floa
 }
 
 void select_greedy(const SelectArgs& a, hipStream_t s) {
-  WCB_LAUNCH(select_partial_kernel, dim3(a.nchunk, a.M), dim3(256), 0, s, a);
+  if (a.seeds) WCB_LAUNCH(select_partial_kernel<true>, dim3(a.nchunk, a.M), dim3(256), 0, s, a);
+  else WCB_LAUNCH(select_partial_kernel<false>, dim3(a.nchunk, a.M), dim3(256), 0, s, a);
   select_finalize(a, s);
 }
 

@@ -130,6 +130,11 @@ struct GemmArgs {
   // profiling (stamps pass): the launch's first-workgroup start / last-workgroup end, recorded by the lean
   // kernel inside the replayed decode graph (common.h stamp_commit); null base: off
   struct Stamp* lstamp = nullptr;
+  // LM head, temperature sampling (sel_seeds non-null, with sel_val): the argmax partials compare the
+  // perturbed scores of sample.h — sample_perturb(score, *sel_inv_t, g(sel_seeds[row], *sel_step, column)) —
+  // in the kernels' sampled instantiations; the softmax partials stay those of the raw logits. Both live in
+  // a device buffer of the decode context, so a captured graph holds for every seed and temperature.
+  const uint64_t* sel_seeds = nullptr; const float* sel_inv_t = nullptr;
 };
 
 void gemm(DType t, const GemmArgs& g, hipStream_t s);
@@ -276,6 +281,10 @@ struct SelectArgs {
   float* st = nullptr; int st_w = 16;
   // per-utterance lists (forest.root non-null): row m is clip m; root_bits must then be all zero
   ForestArgs forest;
+  // temperature sampling (seeds non-null: [M] per-row seeds, *inv_t = 1 / T; sample.h): the partials were
+  // compared as perturbed scores, the re-scoring loops perturb their candidates alike, out_score receives the
+  // winner's perturbed score; the log-prob stays raw logit − lse
+  const uint64_t* seeds = nullptr; const float* inv_t = nullptr;
 };
 void select_greedy(const SelectArgs& a, hipStream_t s);          // vocabulary pass + finalize
 void select_finalize(const SelectArgs& a, hipStream_t s);        // partials already written (fused LM head)

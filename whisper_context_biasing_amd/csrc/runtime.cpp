@@ -27,6 +27,7 @@
 
 #include "../../include/wcb.h"
 #include "kernels.h"
+#include "sample.h"
 
 using namespace wcb;
 
@@ -169,14 +170,25 @@ struct DecCtx {
   DevBuf part_max, part_sum, lpbuf;
   hipGraphExec_t gexec_lp = nullptr, gexec_k_lp = nullptr;
   std::string gkey_lp;
+  // temperature sampling (wcb_generate_sampled, wcb_decode_enable_sampling): samp = one 64-bit word holding
+  // the bits of inv_T = 1 / T in its low half, then the per-row seeds [64] — written on the decode stream at
+  // the start of every sampled call, read by the sampled kernels through this stable address, so the
+  // sampled decode's own graphs ([0] without, [1] with token log-probs) hold for every seed and temperature
+  DevBuf samp;
+  hipGraphExec_t gexec_sm[2] = {}, gexec_k_sm[2] = {};
+  std::string gkey_sm[2];
   void drop_graphs() {
-    for (hipGraphExec_t* g : {&gexec, &gexec_k, &gexec_lp, &gexec_k_lp}) {
+    for (hipGraphExec_t* g : {&gexec, &gexec_k, &gexec_lp, &gexec_k_lp, &gexec_sm[0], &gexec_sm[1], &gexec_k_sm[0],
+                              &gexec_k_sm[1]}) {
       if (*g) (void)hipGraphExecDestroy(*g);
       *g = nullptr;
     }
     gkey.clear();
     gkey_lp.clear();
+    gkey_sm[0].clear();
+    gkey_sm[1].clear();
   }
+  std::string all_gkeys() const { return gkey + gkey_lp + gkey_sm[0] + gkey_sm[1]; }
   // per-utterance bias forest of the call decoding in this context: device buffer carved by the capacities
   // (states, transitions, root children; they only grow: quiesce + realloc, the graph key names them), the
   // pinned staging copy the asynchronous upload reads, and the event of the last upload from it
@@ -1324,6 +1336,9 @@ struct StepCfg {
   // greedy select, token log-probs: [B][out_ld] f32 beside the ids (the context's lpbuf; ensure_lp_ws) — the LM
   // head then also writes its softmax partials and the finalize merges them. Null: the step as it always was
   float* logprob_out = nullptr;
+  // greedy select, temperature sampling: the context's samp words (inv_T, then the seed of every row). Null:
+  // the step as it always was
+  const uint64_t* samp = nullptr;
 };
 
 // the residual's fragment-major copy applies (lean path): the lean LayerNorm table covers d, every
@@ -1600,6 +1615,10 @@ void decode_rows(wcb_handle* h, const StepCfg& c, int b0, int nb, int chain, hip
         lm.sel_max = D.part_max.as<float>() + (size_t)b0 * D.nchunk;
         lm.sel_sum = D.part_sum.as<float>() + (size_t)b0 * D.nchunk;
       }
+      if (c.samp) {   // temperature sampling: the sampled LM head compares perturbed scores
+        lm.sel_inv_t = reinterpret_cast<const float*>(c.samp);
+        lm.sel_seeds = c.samp + 1 + b0;
+      }
     }
     if (lm_tiled) {
       proj("lm_head", lm);
@@ -1678,6 +1697,7 @@ void decode_step(wcb_handle* h, const StepCfg& c) {
     if (c.logprob_out) {
       s.part_max = D.part_max.as<float>(); s.part_sum = D.part_sum.as<float>(); s.out_logprob = c.logprob_out;
     }
+    if (c.samp) { s.inv_t = reinterpret_cast<const float*>(c.samp); s.seeds = c.samp + 1; }
     if (c.embedded) {   // the next step's input embedding in the same launch (embed()'s outputs)
       const bool r32 = h->dec_gemm && lnf_possible(h);
       s.emb = h->tok_emb; s.pemb = h->dec_pos; s.n_pos = h->d.n_text_ctx; s.d = d; s.dtype = h->dt;
@@ -1816,6 +1836,25 @@ ForestDev install_forest(wcb_handle* h, DecCtx& D, const wcb_bias_batch* bb) {
   return F;
 }
 
+// Temperature sampling of a decode in context D: inv_T = 1 / T and the per-row seeds into the context's samp
+// words, stream-ordered on the decode stream and passed by value (write_i32: the caller's array is not read
+// after the call returns, async_out and several contexts in flight included). The allocation is made once.
+constexpr int kSampRows = 64;
+void check_sampling(float temperature, const uint64_t* seeds) {
+  REQUIRE(seeds, "sampling: seeds is required");
+  REQUIRE(std::isfinite(temperature) && temperature > 0.f, "sampling: temperature must be finite and > 0");
+}
+const uint64_t* install_sampling(DecCtx& D, float temperature, const uint64_t* seeds, int rows) {
+  REQUIRE(rows >= 1 && rows <= kSampRows, "sampling: 1 .. 64 rows");
+  D.samp.ensure((size_t)(1 + kSampRows) * 8);
+  int w[2 + 2 * kSampRows] = {};
+  const float inv_t = 1.0f / temperature;
+  std::memcpy(w, &inv_t, 4);
+  std::memcpy(w + 2, seeds, (size_t)rows * 8);
+  write_i32(D.samp.as<int>(), w, 2 + 2 * rows, D.hs);
+  return D.samp.as<uint64_t>();
+}
+
 // Lt: the total length cap (prefix + max new tokens, MaxLength), Tc: cache positions, Lg: max new tokens
 BeamArgs beam_args(wcb_handle* h, DecCtx& D, int B, int nb, int P, int Lt, int Tc, int Lg, int min_new, float lam,
                    const wcb_bias* bs) {
@@ -1876,12 +1915,17 @@ int wcb_encode(wcb_handle* h, const float* mel, int B, void* enc_out, void* stre
 // wcb_generate / wcb_generate_biased: one shared automaton `bias` (or none), or the per-utterance forest `bb`
 static void generate_impl(wcb_handle* h, const float* mel, int B, const wcb_gen_cfg* cfg, const wcb_bias* bias,
                           const wcb_bias_batch* bb, const int32_t* prefix, int prefix_len, int32_t* out_ids,
-                          int32_t* out_steps, void* stream, float* out_logprobs = nullptr, float* out_seq_scores = nullptr) {
+                          int32_t* out_steps, void* stream, float* out_logprobs = nullptr, float* out_seq_scores = nullptr,
+                          const wcb_sample_cfg* smp = nullptr) {
   {
     REQUIRE(h && cfg && out_ids && out_steps && B > 0, "bad argument");
     if (!h->ready) throw WcbError(WCB_ERR_STATE, "weights not finalized");
     const int nb = cfg->num_beams;
     REQUIRE(nb >= 1 && nb <= kMaxBeams, "num_beams must be in [1, 8]");
+    if (smp) {
+      check_sampling(smp->temperature, smp->seeds);
+      if (nb > 1) throw WcbError(WCB_ERR_UNSUPPORTED, "sampling is greedy only (num_beams = 1)");
+    }
     if (nb > 1 && out_logprobs)
       throw WcbError(WCB_ERR_UNSUPPORTED, "token log-probs are greedy only (beam search: out_seq_scores)");
     if (nb == 1 && out_seq_scores)
@@ -1964,6 +2008,7 @@ static void generate_impl(wcb_handle* h, const float* mel, int B, const wcb_gen_
       sc.logprob_out = D.lpbuf.as<float>();
       HIPCHK(hipMemsetAsync(D.lpbuf.p, 0, (size_t)R * out_ld * 4, D.hs));
     }
+    if (smp) sc.samp = install_sampling(D, smp->temperature, smp->seeds, R);
     // prompt positions 0 .. P-2 in causal prefill passes, then the last prompt token is the first
     // decode step's input
     for (int p0 = 0, np; p0 + 1 < P; p0 += np) {
@@ -1993,10 +2038,12 @@ static void generate_impl(wcb_handle* h, const float* mel, int B, const wcb_gen_
     // "all finished" flag once per chunk.
     const int chunk = h->steps_per_graph;
     int done = 0, steps = 0;
-    // (a scored decode has its own graphs and key: neither kind of call evicts the other's)
-    hipGraphExec_t& gexec = out_logprobs ? D.gexec_lp : D.gexec;
-    hipGraphExec_t& gexec_k = out_logprobs ? D.gexec_k_lp : D.gexec_k;
-    std::string& gkey = out_logprobs ? D.gkey_lp : D.gkey;
+    // (a scored decode has its own graphs and key: neither kind of call evicts the other's; so has a sampled
+    // one, without and with log-probs — its key is the same string: never the seeds or the temperature)
+    const int lpi = out_logprobs ? 1 : 0;
+    hipGraphExec_t& gexec = smp ? D.gexec_sm[lpi] : out_logprobs ? D.gexec_lp : D.gexec;
+    hipGraphExec_t& gexec_k = smp ? D.gexec_k_sm[lpi] : out_logprobs ? D.gexec_k_lp : D.gexec_k;
+    std::string& gkey = smp ? D.gkey_sm[lpi] : out_logprobs ? D.gkey_lp : D.gkey;
     if (use_graph && (!gexec || gkey != key)) {
       if (gexec) { (void)hipGraphExecDestroy(gexec); gexec = nullptr; }
       if (gexec_k) { (void)hipGraphExecDestroy(gexec_k); gexec_k = nullptr; }
@@ -2115,6 +2162,16 @@ int wcb_generate_scored(wcb_handle* h, const float* mel, int B, const wcb_gen_cf
   });
 }
 
+int wcb_generate_sampled(wcb_handle* h, const float* mel, int B, const wcb_gen_cfg* cfg, const wcb_sample_cfg* smp,
+                         const wcb_bias* bias, const wcb_bias_batch* bb, const int32_t* prefix, int prefix_len,
+                         int32_t* out_ids, float* out_logprobs, int32_t* out_steps, void* stream) {
+  return guarded(h, [&] {
+    REQUIRE(smp, "wcb_generate_sampled: the sampling configuration is required (wcb_generate_scored decodes without one)");
+    REQUIRE(!(bias && bb), "wcb_generate_sampled: a shared automaton or a bias batch, not both");
+    generate_impl(h, mel, B, cfg, bias, bb, prefix, prefix_len, out_ids, out_steps, stream, out_logprobs, nullptr, smp);
+  });
+}
+
 // ---- step-wise greedy decoding (SURVEY §8(b) wcb_decode_begin / wcb_decode_step): the decode step
 // of wcb_generate, one token per call, on the decode context kMaxCtx-1 (its own stream and buffers,
 // so generate() calls on contexts 0 .. nctx-1 are unaffected); eager launches (the caller inspects
@@ -2130,6 +2187,7 @@ struct wcb_state {
   bool forest = false;   // per-utterance lists installed (wcb_decode_bias_batch): every step takes bias = NULL
   ForestDev fd;
   bool logprobs = false; // wcb_decode_enable_logprobs: every step also writes its column of the context's lpbuf
+  bool sampling = false; // wcb_decode_enable_sampling: every step draws its tokens (the context's samp words)
 };
 
 // step-wise beam search: the beam path of wcb_generate one step per call (begin: cross-K/V of the
@@ -2297,6 +2355,7 @@ int wcb_decode_step(wcb_handle* h, wcb_state* st, const wcb_bias* bias, int32_t*
       sc.score_out = scores;
       sc.embedded = true;   // (wcb_decode_begin embedded the first input; each finalize embeds the next)
       if (st->logprobs) sc.logprob_out = D.lpbuf.as<float>();
+      if (st->sampling) sc.samp = D.samp.as<uint64_t>();
     }
     if (st->forest) sc.forest = &st->fd;
     decode_step(h, sc);
@@ -2397,6 +2456,18 @@ int wcb_decode_enable_logprobs(wcb_handle* h, wcb_state* st) {
     ensure_lp_ws(h, D, st->B, st->max_new);
     HIPCHK(hipMemsetAsync(D.lpbuf.p, 0, (size_t)st->B * st->max_new * 4, D.hs));
     st->logprobs = true;
+  });
+}
+
+int wcb_decode_enable_sampling(wcb_handle* h, wcb_state* st, float temperature, const uint64_t* seeds) {
+  return guarded(h, [&] {
+    REQUIRE(h && st && st->h == h && h->step_state == st, "bad argument (state of this handle)");
+    check_sampling(temperature, seeds);
+    if (st->nb > 1) throw WcbError(WCB_ERR_UNSUPPORTED, "sampling is greedy only (a beam-search state)");
+    if (st->fwd != 0) throw WcbError(WCB_ERR_STATE, "wcb_decode_enable_sampling on a forward cache (wcb_forward_cached state)");
+    if (st->steps != 0) throw WcbError(WCB_ERR_STATE, "wcb_decode_enable_sampling: after the first step (right after wcb_decode_begin)");
+    install_sampling(h->dc[wcb_handle::kMaxCtx - 1], temperature, seeds, st->B);
+    st->sampling = true;
   });
 }
 
@@ -2661,7 +2732,7 @@ void wcb_bias_destroy(wcb_bias* b) {
     } catch (...) {
     }
     for (DecCtx& D : h->dc)
-      if ((D.gkey + D.gkey_lp).find("/" + std::to_string(b->id) + "/") != std::string::npos) D.drop_graphs();
+      if (D.all_gkeys().find("/" + std::to_string(b->id) + "/") != std::string::npos) D.drop_graphs();
     h->biases.erase(std::remove(h->biases.begin(), h->biases.end(), b), h->biases.end());
   }
   for (DevBuf* x : {&b->root_bits, &b->root_child, &b->trans_off, &b->trans_tok, &b->trans_dst, &b->st_depth, &b->st_keep})
@@ -2865,13 +2936,19 @@ int wcb_op_gemm_ln(int dtype, const float* X, const float* ln_w, const float* ln
   });
 }
 
-int wcb_op_lm_head_lse(int dtype, const void* A, const void* W, int M, int V, int K, int walkers, float* logits, long ld,
-                       float* lse, int32_t* argmax, void* stream) {
+// wcb_op_lm_head_lse, and wcb_op_lm_head_sample (seeds non-null: the sampled kernels, step on the device)
+static int op_lm_head(int dtype, const void* A, const void* W, int M, int V, int K, int walkers, float* logits, long ld,
+                      float* lse, int32_t* argmax, void* stream, bool sampled, float temperature, const uint64_t* seeds,
+                      int step) {
   return guarded(nullptr, [&] {
     REQUIRE(A && W && logits && lse && argmax && M > 0 && M <= 64 && V > 0 && K > 0 && ld >= V,
             "bad argument (1 <= M <= 64, ld >= V, every pointer)");
     REQUIRE(dtype >= WCB_BF16 && dtype <= WCB_F32, "dtype");
     REQUIRE(walkers >= 0 && walkers <= 4096, "walkers: 0 (default) .. 4096");
+    if (sampled) {
+      check_sampling(temperature, seeds);
+      REQUIRE(step >= 0, "step must be >= 0");
+    }
     const DType dt = DType(dtype);
     // the widths the decode step's LM head runs at: the decode GEMM's column walk, or the older skinny kernel
     if (!gemm_dec_supported(dt, K) && K != 32 && K != 2560)
@@ -2879,7 +2956,7 @@ int wcb_op_lm_head_lse(int dtype, const void* A, const void* W, int M, int V, in
     hipStream_t st = (hipStream_t)stream;
     const int wk = walkers > 0 ? walkers : kDecWalkers;
     const int nchunk = lm_head_partials(dt, K, V, wk);
-    struct Scratch { DevBuf b; ~Scratch() { b.release(); } } pv, pi, pm, ps, zero, wpad, wfm;
+    struct Scratch { DevBuf b; ~Scratch() { b.release(); } } pv, pi, pm, ps, zero, wpad, wfm, samp;
     const size_t np = (size_t)M * nchunk * 4;
     pv.b.ensure(np); pi.b.ensure(np); pm.b.ensure(np); ps.b.ensure(np); zero.b.ensure(16);
     GemmArgs lm = drow(A, K, W, M, V, K, logits, ld);
@@ -2888,6 +2965,18 @@ int wcb_op_lm_head_lse(int dtype, const void* A, const void* W, int M, int V, in
     lm.sel_val = pv.b.as<float>(); lm.sel_idx = pi.b.as<int>();
     lm.sel_max = pm.b.as<float>(); lm.sel_sum = ps.b.as<float>();
     lm.sel_step = zero.b.as<int>();   // step 0 against min_new 0: no EOS mask; lam 0: no boost
+    if (sampled) {   // [0] the step counter, then inv_T and the seeds laid out as a decode context's samp words
+      samp.b.ensure(8 + (size_t)(1 + M) * 8);
+      int w[4 + 2 * 64] = {};
+      const float inv_t = 1.0f / temperature;
+      w[0] = step;
+      std::memcpy(w + 2, &inv_t, 4);
+      std::memcpy(w + 4, seeds, (size_t)M * 8);
+      write_i32(samp.b.as<int>(), w, 4 + 2 * M, st);
+      lm.sel_step = samp.b.as<int>();   // (min_new 0: still no EOS mask)
+      lm.sel_inv_t = reinterpret_cast<const float*>(samp.b.as<int>() + 2);
+      lm.sel_seeds = samp.b.as<uint64_t>() + 2;
+    }
     int nw = 0, kpw = 0;
     if (dt != kF32 && gemm_dec_supported(dt, K) && lean_cfg(K, nw, kpw)) {
       // as the runtime's token embedding: a fragment-major copy of whole 16-row tiles, zero rows past V
@@ -2902,6 +2991,24 @@ int wcb_op_lm_head_lse(int dtype, const void* A, const void* W, int M, int V, in
     lm_head_lse_finalize(lm.sel_val, lm.sel_idx, lm.sel_max, lm.sel_sum, M, nchunk, lse, argmax, st);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st));   // the scratch buffers are freed on return
+  });
+}
+
+int wcb_op_lm_head_lse(int dtype, const void* A, const void* W, int M, int V, int K, int walkers, float* logits, long ld,
+                       float* lse, int32_t* argmax, void* stream) {
+  return op_lm_head(dtype, A, W, M, V, K, walkers, logits, ld, lse, argmax, stream, false, 0.f, nullptr, 0);
+}
+
+int wcb_op_lm_head_sample(int dtype, const void* A, const void* W, int M, int V, int K, int walkers, float temperature,
+                          const uint64_t* seeds, int step, float* logits, long ld, float* lse, int32_t* sampled,
+                          void* stream) {
+  return op_lm_head(dtype, A, W, M, V, K, walkers, logits, ld, lse, sampled, stream, true, temperature, seeds, step);
+}
+
+int wcb_sample_noise(uint64_t seed, int step, int v0, int n, float* out) {
+  return guarded(nullptr, [&] {
+    REQUIRE(out && n >= 0 && step >= 0 && v0 >= 0 && (long)v0 + n <= 0x7fffffffL, "bad argument (out, n, step, v0 >= 0)");
+    for (int i = 0; i < n; ++i) out[i] = sample_noise(seed, step, v0 + i);
   });
 }
 

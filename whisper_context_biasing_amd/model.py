@@ -20,6 +20,8 @@ memory and streams. There is no CPU fallback.
 from __future__ import annotations
 
 import ctypes as C
+import math
+import zlib
 from collections import OrderedDict
 from dataclasses import dataclass
 from types import SimpleNamespace
@@ -42,6 +44,44 @@ def _stream(device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
 
+_M64 = (1 << 64) - 1
+
+
+def _mix64(z: int) -> int:
+    """splitmix64's finaliser: a bijection of the 64-bit integers."""
+    z &= _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def clip_seeds(seed: int, first_clip: int, n: int, attempt: int = 0) -> np.ndarray:
+    """The per-clip 64-bit sampling seeds an int `seed` stands for: clip c (its index in the WHOLE batch) of
+    fallback attempt a draws with  mix64(mix64(seed) + (a << 32 | c))  (mix64 = splitmix64's finaliser, sums
+    mod 2^64). Returns the seeds of clips first_clip .. first_clip + n - 1 as uint64 [n]. A pure function:
+    mix64 is a bijection, so distinct (clip < 2^32, attempt < 2^32) give distinct seeds, a batch split anywhere
+    gives the values of the unsplit batch, and every attempt draws fresh noise."""
+    if not (0 <= int(first_clip) and int(first_clip) + int(n) <= 1 << 32 and 0 <= int(attempt) < 1 << 32):
+        raise ValueError("clip_seeds: clip indices and attempt must fit 32 bits")
+    base = _mix64(int(seed))
+    return np.asarray([_mix64(base + ((int(attempt) << 32) | c)) for c in range(int(first_clip), int(first_clip) + int(n))],
+                      dtype=np.uint64)
+
+
+def compression_ratio(ids, vocab: int, eos: Optional[int] = None) -> float:
+    """HF's `_retrieve_compression_ratio` ([tf] generation_whisper.py) of one clip's tokens: those before the
+    first `eos` (all of them when eos is None or absent), each written as int(log2(vocab) / 8) + 1 little-endian
+    bytes; len(bytes) / len(zlib.compress(bytes)). No tokens: 0.0."""
+    toks = [int(t) for t in np.asarray(ids).reshape(-1)]
+    if eos is not None and int(eos) in toks:
+        toks = toks[:toks.index(int(eos))]
+    if not toks:
+        return 0.0
+    length = int(math.log2(vocab) / 8) + 1
+    data = b"".join(t.to_bytes(length, "little") for t in toks)
+    return len(data) / len(zlib.compress(data))
+
+
 @dataclass
 class GenerateOutput:
     sequences: torch.Tensor
@@ -52,6 +92,8 @@ class GenerateOutput:
     token_logprobs: Optional[torch.Tensor] = None
     avg_logprob: Optional[torch.Tensor] = None
     sequences_scores: Optional[torch.Tensor] = None
+    # generate(temperature=(t0, t1, ...)): the temperature each clip's result was decoded at, [B] f32
+    temperatures: Optional[torch.Tensor] = None
 
 
 @dataclass
@@ -478,7 +520,9 @@ class WhisperCB:
                  num_beams: Optional[int] = None, bias_list=None, bias_boost: float = 0.0,
                  min_new_tokens: int = 0, prompt_ids=None, return_dict_in_generate: bool = False,
                  generation_config=None, use_graph: bool = True, block: bool = True, bias_lists=None,
-                 per_utterance_bias: bool = False, output_logprobs: bool = False, **kwargs):
+                 per_utterance_bias: bool = False, output_logprobs: bool = False, temperature=0.0, seed=0,
+                 do_sample: Optional[bool] = None, logprob_threshold: Optional[float] = -1.0,
+                 compression_ratio_threshold: Optional[float] = 2.4, **kwargs):
         """Greedy (num_beams = 1, the reference's eval setting) or HF beam
         search (num_beams = 2..8, [tf] generation/utils.py:3208) on the device.
 
@@ -507,18 +551,58 @@ class WhisperCB:
         With `block=False` the result is a GenerateOutput of device views valid after `synchronize()`:
         `sequences` the int32 generated columns, `token_logprobs` / `sequences_scores`; `avg_logprob` is a
         host computation and stays None.
+
+        `temperature > 0` (or `do_sample=True`, temperature then defaulting to 1.0) samples every token from
+        softmax(score / temperature) on the device (wcb_generate_sampled; greedy only: `num_beams` must be 1),
+        score = logit + bias boost; token log-probs keep their meaning (raw logits). `seed` = an int, expanded
+        per clip by `clip_seeds(seed, 0, B)`, or a sequence of B 64-bit per-clip seeds; the same seeds give the
+        same tokens whatever the batch split. `temperature=0` (the default) is the call as it always was.
+
+        `temperature=(0.0, 0.2, ...)` (a sequence) runs Whisper's temperature fallback (HF
+        `generate_with_fallback`, greedy and sampling only): attempt i decodes the still-failing clips at
+        temperature[i] with log-probs; a clip fails when its avg_logprob < `logprob_threshold` or its
+        `compression_ratio` > `compression_ratio_threshold` (None disables either); a clip that passes keeps
+        that result, one that fails at the last temperature keeps the last. An int seed gives attempt i
+        `clip_seeds(seed, 0, B, attempt=i)`, explicit per-clip seeds s_b give s_b + i·0x9E3779B97F4A7C15 (mod
+        2^64). Returns a GenerateOutput with `temperatures` [B]. Failing clips are re-encoded from their mel.
         """
         if not self._loaded:
             raise _lib.WcbError("weights not loaded")
         if output_logprobs:
             return_dict_in_generate = True
         x_all = self._features(input_features)
+        if isinstance(temperature, (list, tuple, np.ndarray)):
+            if not block:
+                raise ValueError("temperature fallback reads every attempt's scores: block=False is not supported")
+            return self._generate_with_fallback(
+                x_all, [float(t) for t in temperature], seed, logprob_threshold, compression_ratio_threshold,
+                dict(labels=labels, bias_spans=bias_spans, max_length=max_length, num_beams=num_beams, bias_list=bias_list,
+                     bias_boost=bias_boost, min_new_tokens=min_new_tokens, prompt_ids=prompt_ids,
+                     generation_config=generation_config, use_graph=use_graph, bias_lists=bias_lists,
+                     per_utterance_bias=per_utterance_bias))
+        T = float(temperature)
+        if do_sample and T == 0.0:
+            T = 1.0
+        if do_sample is False:
+            T = 0.0
+        if not (T >= 0.0 and math.isfinite(T)):
+            raise ValueError(f"temperature must be finite and >= 0, got {temperature!r}")
+        seeds = None   # uint64 [B] of the whole batch when sampling
+        if T > 0.0:
+            if isinstance(seed, (int, np.integer)):
+                seeds = clip_seeds(int(seed), 0, x_all.shape[0])
+            else:
+                seeds = np.ascontiguousarray(np.asarray([int(v) & _M64 for v in seed], dtype=np.uint64))
+                if seeds.shape[0] != x_all.shape[0]:
+                    raise ValueError(f"seed has {seeds.shape[0]} entries, the batch {x_all.shape[0]} clips")
         if bias_lists is None and per_utterance_bias and bias_list is None and bias_boost > 0 and bias_spans is not None:
             bias_lists = self._spans_to_lists(bias_spans)
         if bias_lists is not None:   # checked on the whole batch, before any split
             bias_lists, bias_list = self._clip_lists(bias_lists, bias_list, x_all.shape[0]), None
         nb_req = int(num_beams if num_beams is not None else getattr(generation_config or self.generation_config,
                                                                       "num_beams", 1) or 1)
+        if seeds is not None and nb_req != 1:
+            raise ValueError("sampling (temperature > 0) is greedy only: num_beams must be 1")
         per_call = self.max_clips_per_call(nb_req)
         if x_all.shape[0] > per_call:
             # the library takes at most 64 clips (512 decoder rows) per call: split, decode in order,
@@ -530,8 +614,11 @@ class WhisperCB:
                       output_logprobs=output_logprobs)
             if bias_lists is None and bias_list is None and bias_boost > 0 and bias_spans is not None:
                 kw["bias_list"], kw["bias_spans"] = self._spans_to_phrases(bias_spans), None
+            if seeds is not None:
+                kw["temperature"] = T
             parts = [self.generate(x_all[i:i + per_call],
-                                   bias_lists=bias_lists[i:i + per_call] if bias_lists is not None else None, **kw)
+                                   bias_lists=bias_lists[i:i + per_call] if bias_lists is not None else None,
+                                   **(dict(kw, seed=seeds[i:i + per_call]) if seeds is not None else kw))
                      for i in range(0, x_all.shape[0], per_call)]
             seqs = [p.sequences if return_dict_in_generate else p for p in parts]
             Wd = max(t.shape[1] for t in seqs)
@@ -576,9 +663,21 @@ class WhisperCB:
         out = torch.empty(B, max_new, dtype=torch.int32, device=self.device)
         steps = C.c_int32(0)
         pre = np.asarray(prefix, dtype=np.int32)
+        smp = _lib.WcbSampleCfg(T, seeds.ctypes.data_as(C.POINTER(C.c_uint64))) if seeds is not None else None
         if output_logprobs:
-            return self._generate_scored(x, cfg, bl, bias_lists if bias_boost > 0 else None, prefix, pre, out, block)
-        if bias_lists is not None and bias_boost > 0:
+            return self._generate_scored(x, cfg, bl, bias_lists if bias_boost > 0 else None, prefix, pre, out, block, smp)
+        if smp is not None:
+            bb = BiasBatch(self, bias_lists) if (bias_lists is not None and bias_boost > 0) else None
+            try:
+                _lib.check(self._lib.wcb_generate_sampled(self._h, _ptr(x), B, C.byref(cfg), C.byref(smp),
+                                                          bl._h if (bl and not bb) else None, bb._h if bb else None,
+                                                          pre.ctypes.data if len(prefix) > 1 else None, len(prefix),
+                                                          _ptr(out), None, C.byref(steps), _stream(self.device)),
+                           self._h, "wcb_generate_sampled")
+            finally:
+                if bb:
+                    bb.close()   # the call copied it, as it copied the seeds (also with block=False)
+        elif bias_lists is not None and bias_boost > 0:
             bb = BiasBatch(self, bias_lists)   # per call: not in the automaton LRU
             try:
                 _lib.check(self._lib.wcb_generate_biased(self._h, _ptr(x), B, C.byref(cfg), bb._h,
@@ -600,21 +699,28 @@ class WhisperCB:
             return GenerateOutput(sequences=torch.cat([sot, ids], dim=1))
         return self._whisper_trim(ids)
 
-    def _generate_scored(self, x, cfg, bl, bias_lists, prefix, pre, out, block) -> GenerateOutput:
-        """generate(output_logprobs=True) on one library call: wcb_generate_scored with the shared automaton
-        `bl`, the per-clip `bias_lists`, or neither."""
+    def _generate_scored(self, x, cfg, bl, bias_lists, prefix, pre, out, block, smp=None) -> GenerateOutput:
+        """generate(output_logprobs=True) on one library call: wcb_generate_scored (smp: wcb_generate_sampled)
+        with the shared automaton `bl`, the per-clip `bias_lists`, or neither."""
         B, max_new, beams = x.shape[0], cfg.max_new_tokens, cfg.num_beams > 1
         lp = None if beams else torch.zeros(B, max_new, dtype=torch.float32, device=self.device)
         ss = torch.zeros(B, dtype=torch.float32, device=self.device) if beams else None
         steps = C.c_int32(0)
         bb = BiasBatch(self, bias_lists) if bias_lists is not None else None   # per call: not in the automaton LRU
         try:
-            _lib.check(self._lib.wcb_generate_scored(self._h, _ptr(x), B, C.byref(cfg), bl._h if (bl and not bb) else None,
-                                                     bb._h if bb else None,
-                                                     pre.ctypes.data if len(prefix) > 1 else None, len(prefix),
-                                                     _ptr(out), _ptr(lp) if lp is not None else None,
-                                                     _ptr(ss) if ss is not None else None, C.byref(steps),
-                                                     _stream(self.device)), self._h, "wcb_generate_scored")
+            if smp is not None:
+                _lib.check(self._lib.wcb_generate_sampled(self._h, _ptr(x), B, C.byref(cfg), C.byref(smp),
+                                                          bl._h if (bl and not bb) else None, bb._h if bb else None,
+                                                          pre.ctypes.data if len(prefix) > 1 else None, len(prefix),
+                                                          _ptr(out), _ptr(lp), C.byref(steps), _stream(self.device)),
+                           self._h, "wcb_generate_sampled")
+            else:
+                _lib.check(self._lib.wcb_generate_scored(self._h, _ptr(x), B, C.byref(cfg),
+                                                         bl._h if (bl and not bb) else None, bb._h if bb else None,
+                                                         pre.ctypes.data if len(prefix) > 1 else None, len(prefix),
+                                                         _ptr(out), _ptr(lp) if lp is not None else None,
+                                                         _ptr(ss) if ss is not None else None, C.byref(steps),
+                                                         _stream(self.device)), self._h, "wcb_generate_scored")
         finally:
             if bb:
                 bb.close()   # the call copied it (also with block=False)
@@ -638,20 +744,102 @@ class WhisperCB:
             res.avg_logprob = torch.from_numpy(avg).to(self.device)
         return res
 
+    def _generate_with_fallback(self, x_all, temps, seed, logprob_threshold, compression_ratio_threshold, kw) -> GenerateOutput:
+        """generate(temperature=(t0, t1, ...)): HF's generate_with_fallback rule over generate() calls on the
+        still-failing clips (their mel re-encoded: the rare path pays the encoder again)."""
+        if not temps:
+            raise ValueError("temperature: an empty sequence")
+        B = x_all.shape[0]
+        nb = kw["num_beams"] if kw["num_beams"] is not None else getattr(kw["generation_config"] or self.generation_config,
+                                                                       "num_beams", 1)
+        if int(nb or 1) != 1:
+            raise ValueError("temperature fallback is greedy and sampling only: num_beams must be 1")
+        explicit = None
+        if not isinstance(seed, (int, np.integer)):
+            explicit = [int(v) & _M64 for v in seed]
+            if len(explicit) != B:
+                raise ValueError(f"seed has {len(explicit)} entries, the batch {B} clips")
+        bias_lists, bias_list, bias_spans = kw.pop("bias_lists"), kw.pop("bias_list"), kw.pop("bias_spans")
+        per_utt, boost = kw.pop("per_utterance_bias"), kw["bias_boost"]
+        # the batch's lists once, on the whole batch (as the split path): later attempts decode a subset
+        if bias_lists is None and per_utt and bias_list is None and boost > 0 and bias_spans is not None:
+            bias_lists = self._spans_to_lists(bias_spans)
+        if bias_lists is not None:
+            bias_lists, bias_list = self._clip_lists(bias_lists, bias_list, B), None
+        elif bias_list is None and boost > 0 and bias_spans is not None:
+            bias_list = self._spans_to_phrases(bias_spans)
+        kw.pop("labels")
+        seqs, lps = [None] * B, [None] * B
+        avg, used = np.zeros(B, dtype=np.float32), np.zeros(B, dtype=np.float32)
+        todo = np.arange(B)
+        P = 1 + (len(kw["prompt_ids"]) if kw["prompt_ids"] is not None else 0)
+        for i, T in enumerate(temps):
+            if explicit is not None:
+                sd = np.asarray([(explicit[b] + i * 0x9E3779B97F4A7C15) & _M64 for b in todo], dtype=np.uint64)
+            else:
+                sd = clip_seeds(int(seed), 0, B, attempt=i)[todo]
+            idx = torch.as_tensor(todo, device=x_all.device)
+            res = self.generate(x_all[idx] if len(todo) < B else x_all, temperature=T, seed=sd, output_logprobs=True,
+                                bias_list=bias_list, bias_lists=[bias_lists[b] for b in todo] if bias_lists is not None else None,
+                                **kw)
+            ids_h = res.sequences[:, P:].cpu().numpy()
+            lp_h = res.token_logprobs.cpu().numpy()
+            avg_h = res.avg_logprob.cpu().numpy()
+            fail = []
+            for j, b in enumerate(todo):
+                seqs[b], lps[b], avg[b], used[b] = ids_h[j], lp_h[j], avg_h[j], T
+                bad = logprob_threshold is not None and avg_h[j] < logprob_threshold
+                if not bad and compression_ratio_threshold is not None:
+                    bad = compression_ratio(ids_h[j], self.dims.vocab, self.dims.eos_token_id) > compression_ratio_threshold
+                if bad:
+                    fail.append(b)
+            todo = np.asarray(fail, dtype=np.int64)
+            if not len(todo):
+                break
+        # joined per clip, padded as the split path pads: ids with pad, log-probs with 0
+        W = max(len(r) for r in seqs)
+        ids = np.full((B, W), self.dims.pad_token_id, dtype=np.int64)
+        lp = np.zeros((B, W), dtype=np.float32)
+        for b in range(B):
+            ids[b, :len(seqs[b])] = seqs[b]
+            lp[b, :len(lps[b])] = lps[b]
+        prefix = ([int(t) for t in kw["prompt_ids"]] if kw["prompt_ids"] is not None else []) + [self.dims.decoder_start_token_id]
+        sot = np.broadcast_to(np.asarray(prefix, dtype=np.int64), (B, len(prefix)))
+        dev = self.device
+        return GenerateOutput(sequences=torch.from_numpy(np.concatenate([sot, ids], axis=1)).to(dev),
+                              token_logprobs=torch.from_numpy(lp).to(dev), avg_logprob=torch.from_numpy(avg).to(dev),
+                              temperatures=torch.from_numpy(used).to(dev))
+
     def decode_begin(self, encoder_outputs, prompt_ids=None, bias_list=None, bias_boost: float = 0.0,
                      min_new_tokens: int = 0, num_beams: int = 1, max_length: Optional[int] = None,
-                     bias_lists=None, logprobs: bool = False) -> "StepDecoder":
+                     bias_lists=None, logprobs: bool = False, temperature: float = 0.0, seed=0) -> "StepDecoder":
         """Step-wise decoding from an encoder output [B, 1500, d] (this model's dtype, on its device): the
         streaming form of generate() (wcb_decode_begin / wcb_decode_begin_beams). Greedy (num_beams = 1) or
         beam search (num_beams 2..8; `max_length` = generate()'s, the beams' length cap: None = the
         max_target_positions cap). `prompt_ids` = one prompt for every clip or a [B, P] array of per-clip
         prompts (decoder_start_token_id is appended as generate() does). `bias_lists` = per-clip phrase lists as
         generate() takes them (wcb_decode_bias_batch; a shared `bias_list` of phrases is appended to each).
-        `logprobs=True` (greedy): StepDecoder.logprobs() gives the token log-probs of the steps taken."""
+        `logprobs=True` (greedy): StepDecoder.logprobs() gives the token log-probs of the steps taken.
+        `temperature > 0` (greedy): every step samples as generate(temperature=..., seed=...) does
+        (wcb_decode_enable_sampling; `seed` an int through clip_seeds, or B per-clip seeds); step()'s scores are
+        then the winners' perturbed values."""
         enc = self._encoder_state(encoder_outputs)   # [B, 1500, d] checked: the library copies B·1500·d
         B = enc.shape[0]
         if B > 64:
             raise ValueError("decode_begin takes at most 64 clips")
+        T = float(temperature)
+        if not (T >= 0.0 and math.isfinite(T)):
+            raise ValueError(f"temperature must be finite and >= 0, got {temperature!r}")
+        seeds = None
+        if T > 0.0:
+            if int(num_beams) != 1:
+                raise ValueError("sampling (temperature > 0) is greedy only: num_beams must be 1")
+            if isinstance(seed, (int, np.integer)):
+                seeds = clip_seeds(int(seed), 0, B)
+            else:
+                seeds = np.ascontiguousarray(np.asarray([int(v) & _M64 for v in seed], dtype=np.uint64))
+                if seeds.shape[0] != B:
+                    raise ValueError(f"seed has {seeds.shape[0]} entries, the batch {B} clips")
         start = self.dims.decoder_start_token_id
         if prompt_ids is None:
             pre = None
@@ -683,6 +871,9 @@ class WhisperCB:
         dec = StepDecoder(self, st, B, bl, nb)
         if logprobs:   # greedy only (wcb.h): every step records the log-prob of its token
             _lib.check(self._lib.wcb_decode_enable_logprobs(self._h, st), self._h, "wcb_decode_enable_logprobs")
+        if seeds is not None:
+            _lib.check(self._lib.wcb_decode_enable_sampling(self._h, st, T, seeds.ctypes.data_as(C.POINTER(C.c_uint64))),
+                       self._h, "wcb_decode_enable_sampling")
         if bias_lists is not None and bias_boost > 0:
             bb = BiasBatch(self, bias_lists)
             try:
