@@ -334,6 +334,38 @@ int wcb_op_lm_head_sample(int dtype, const void* A, const void* W, int M, int V,
 /* HOST, no GPU: out[i] = g(seed, step, v0 + i), the same inline function the kernels compile */
 int wcb_sample_noise(uint64_t seed, int step, int v0, int n, float* out);
 
+/* ---- token rules of the greedy decoder: deny lists and Whisper's timestamp grammar, applied on the chip at
+ * every step (HF SuppressTokensLogitsProcessor, SuppressTokensAtBeginLogitsProcessor and
+ * WhisperTimeStampLogitsProcessor with _detect_timestamp_from_logprob; semantics: csrc/tsrule.h).
+ * With t tokens generated after the prompt: `suppress` ids are never chosen, `begin_suppress` ids not at t == 0;
+ * with timestamps = 1 the row follows the timestamp grammar over the ids >= timestamp_begin (pairs, never
+ * decreasing, a first timestamp of at most timestamp_begin + max_initial_timestamp_index, a timestamp whenever
+ * the timestamps' summed probability exceeds the best text token's) and no_timestamps_token_id is never chosen.
+ * A row whose every token is excluded emits EOS. Token log-probs are unaffected (raw log-softmax). */
+typedef struct { const int32_t* suppress; int n_suppress;
+                 const int32_t* begin_suppress; int n_begin_suppress;
+                 int timestamps;                 /* 0 / 1 */
+                 int timestamp_begin, no_timestamps_token_id;   /* read with timestamps = 1 */
+                 int max_initial_timestamp_index; /* < 0: no limit */ } wcb_token_rules;
+/* Handle state, like a generation config: applies to every greedy decode begun afterwards (wcb_generate, _biased,
+ * _scored, _sampled, wcb_decode_begin / wcb_decode_step); NULL removes the rules. Waits for queued work, then
+ * uploads the two deny bitmaps into handle-owned buffers. WCB_ERR_STATE before wcb_finalize_weights or while a
+ * step-wise decode is open; WCB_ERR_ARG for an id outside [0, vocab), timestamp_begin outside (eos, vocab), or,
+ * with timestamps = 1, a deny id >= timestamp_begin. With rules installed num_beams > 1 is WCB_ERR_UNSUPPORTED;
+ * with timestamps = 1 so is a sampled decode. Ruled decodes replay captured graphs of their own. */
+int wcb_set_token_rules(wcb_handle*, const wcb_token_rules* /* NULL: none */);
+/* HOST, no GPU: scores[vocab] of a row that generated `generated[0..n)`: -inf written exactly where the device
+ * excludes a token (rule 5 in double), so argmax(scores) is the device's token (all -inf: EOS). */
+int wcb_token_rules_apply_host(const wcb_token_rules*, int vocab, int eos, const int32_t* generated, int n,
+                               float* scores);
+/* The LM head with the deny bitmap plus the rule reduction of the finalize on caller operands (as
+ * wcb_op_lm_head_lse; lam = 0, no EOS mask): row m has generated `generated[m·gen_ld .. + lens[m])` (HOST);
+ * next_ids[M] int32 DEVICE. Rows at t == 0 and t > 0 in one call with begin_suppress ids and no timestamps:
+ * WCB_ERR_ARG (the bitmap of a launch is chosen by its step). */
+int wcb_op_lm_head_rules(int dtype, const void* A, const void* W, int M, int V, int K, int walkers,
+                         const wcb_token_rules* rules, int eos, const int32_t* generated, int gen_ld,
+                         const int32_t* lens, float* logits, long ld, int32_t* next_ids, void* stream);
+
 /* debug counters by name (not part of wcb_profile_read): "graph_captures" = decode graphs instantiated so
  * far on this handle. Unknown name: WCB_ERR_ARG. */
 int wcb_debug_counter(const wcb_handle* h, const char* name, int64_t* out);

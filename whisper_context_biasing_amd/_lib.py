@@ -32,6 +32,26 @@ class WcbSampleCfg(C.Structure):
     _fields_ = [("temperature", C.c_float), ("seeds", C.POINTER(C.c_uint64))]
 
 
+class WcbTokenRules(C.Structure):
+    _fields_ = [("suppress", C.POINTER(C.c_int32)), ("n_suppress", C.c_int),
+                ("begin_suppress", C.POINTER(C.c_int32)), ("n_begin_suppress", C.c_int),
+                ("timestamps", C.c_int), ("timestamp_begin", C.c_int), ("no_timestamps_token_id", C.c_int),
+                ("max_initial_timestamp_index", C.c_int)]
+
+
+def token_rules(suppress=(), begin_suppress=(), timestamps=False, timestamp_begin=0, no_timestamps=0,
+                max_initial_timestamp_index=-1):
+    """A WcbTokenRules and the arrays it points into (keep both alive for the call)."""
+    import numpy as np
+    sup = np.ascontiguousarray(np.asarray(list(suppress), dtype=np.int32))
+    beg = np.ascontiguousarray(np.asarray(list(begin_suppress), dtype=np.int32))
+    p32 = C.POINTER(C.c_int32)
+    r = WcbTokenRules(sup.ctypes.data_as(p32) if len(sup) else None, len(sup),
+                      beg.ctypes.data_as(p32) if len(beg) else None, len(beg), int(bool(timestamps)),
+                      int(timestamp_begin), int(no_timestamps), int(max_initial_timestamp_index))
+    return r, (sup, beg)
+
+
 class WcbTensorView(C.Structure):
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("dtype", C.c_int), ("ndim", C.c_int),
                 ("shape", C.c_int64 * 4), ("stride", C.c_int64 * 4)]
@@ -82,6 +102,10 @@ SIGNATURES = {
     "wcb_op_lm_head_sample": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                         C.POINTER(C.c_uint64), C.c_int, _P, C.c_long, _P, _P, _P]),
     "wcb_sample_noise": (C.c_int, [C.c_uint64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]),
+    "wcb_set_token_rules": (C.c_int, [_P, C.POINTER(WcbTokenRules)]),
+    "wcb_token_rules_apply_host": (C.c_int, [C.POINTER(WcbTokenRules), C.c_int, C.c_int, _P, C.c_int, _P]),
+    "wcb_op_lm_head_rules": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(WcbTokenRules),
+                                       C.c_int, _P, C.c_int, _P, _P, C.c_long, _P, _P]),
     "wcb_debug_counter": (C.c_int, [_P, C.c_char_p, C.POINTER(C.c_int64)]),
     "wcb_debug_copy": (C.c_int, [_P, C.c_char_p, _P, C.c_int64, C.c_int]),
     "wcb_profile_enable": (C.c_int, [_P, C.c_int]),

@@ -89,3 +89,37 @@ def dims_from_hf_config(cfg) -> WhisperDims:
         eos_token_id=cfg.eos_token_id, pad_token_id=cfg.pad_token_id,
         decoder_start_token_id=cfg.decoder_start_token_id,
         n_audio_ctx=cfg.max_source_positions, n_text_ctx=cfg.max_target_positions)
+
+
+N_TIMESTAMPS = 1501         # <|0.00|> .. <|30.00|> in 0.02 s steps, the last ids of every Whisper vocabulary
+TIME_PRECISION = 0.02       # seconds per timestamp step
+
+
+def timestamp_ids(dims):
+    """(timestamp_begin, no_timestamps) of a vocabulary: the 1501 timestamp tokens are its last ids and
+    <|notimestamps|> sits right before them (51864: 50363 / 50362, 51865: 50364 / 50363, 51866: 50365 / 50364)."""
+    vocab = dims.vocab if hasattr(dims, "vocab") else int(dims)
+    timestamp_begin = vocab - N_TIMESTAMPS
+    return timestamp_begin, timestamp_begin - 1
+
+
+def parse_segments(ids, timestamp_begin, eos=None):
+    """Segments of one row of generated ids decoded with timestamps: a list of (start_s, end_s, token_ids). The
+    text between one timestamp token and the next is a segment, time = (token - timestamp_begin) * 0.02 s; of a
+    doubled timestamp the second one starts the next segment; a trailing segment without a closing timestamp has
+    end_s None. The row ends at its first `eos`."""
+    segs, start, toks = [], None, []
+    for t in (int(v) for v in ids):
+        if eos is not None and t == eos:
+            break
+        if t >= timestamp_begin:
+            sec = round((t - timestamp_begin) * TIME_PRECISION, 2)
+            if toks:
+                segs.append((start, sec, toks))
+                toks = []
+            start = sec
+        else:
+            toks.append(t)
+    if toks:
+        segs.append((start, None, toks))
+    return segs

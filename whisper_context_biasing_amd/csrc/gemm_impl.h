@@ -1063,6 +1063,8 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(GemmArgs g) {
     __syncthreads();
   }
   const bool mask_eos = g.sel_val && *g.sel_step < g.sel_min_new;
+  // token rules (wave-uniform, null: none): the deny bitmap of this step
+  const uint32_t* deny = !g.sel_val ? nullptr : (g.sel_deny0 && *g.sel_step == 0) ? g.sel_deny0 : g.sel_deny;
   [[maybe_unused]] int smp_step = 0;
   [[maybe_unused]] float smp_inv_t = 1.f;
   if constexpr (SAMPLE) { smp_step = *g.sel_step; smp_inv_t = *g.sel_inv_t; }
@@ -1116,6 +1118,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(GemmArgs g) {
           x = bias_bonus(x, g.sel_lam, g.sel_rowbase[row] + (int)((g.sel_root_bits[nn >> 5] >> (nn & 31)) & 1u));
         if constexpr (SAMPLE) x = sample_perturb(x, smp_inv_t, sample_noise(g.sel_seeds[row], smp_step, nn));
         if (mask_eos && nn == g.sel_eos) x = -INFINITY;
+        if (deny && deny_bit(deny, nn)) x = -INFINITY;
         xi = nn;
       }
 #pragma unroll
@@ -1340,6 +1343,9 @@ __global__ __launch_bounds__(NW * 64) void gemm_dec_kernel(GemmArgs g) {
   // tile ahead with the weights (read in the epilogue they cost a dependent round trip per tile)
   const bool boost = g.sel_val && g.sel_lam != 0.f;
   uint32_t rbw = boost ? g.sel_root_bits[(ct * 16) >> 5] : 0u, rbn = 0u;
+  // token rules (wave-uniform, null: none): this step's deny bitmap, the tile's word fetched like the root bits
+  const uint32_t* deny = !g.sel_val ? nullptr : (g.sel_deny0 && *g.sel_step == 0) ? g.sel_deny0 : g.sel_deny;
+  uint32_t dnw = deny ? deny[(ct * 16) >> 5] : 0u, dnn = 0u;
   int buf = 0;
   for (; ct < ntile; ct += gridDim.x) {
     const int n0 = ct * 16;
@@ -1349,6 +1355,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_dec_kernel(GemmArgs g) {
     if constexpr (P) {
       load_w(wn[PD - 1], min(ct + PD * (int)gridDim.x, ntile - 1));
       if (boost) rbn = g.sel_root_bits[(min(ct + (int)gridDim.x, ntile - 1) * 16) >> 5];
+      if (deny) dnn = deny[(min(ct + (int)gridDim.x, ntile - 1) * 16) >> 5];
     }
     if constexpr (AM == 3) {
       const T* A = reinterpret_cast<const T*>(g.A) + (long)(n0 / g.a_grp_n) * g.a_grp_off;
@@ -1421,6 +1428,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_dec_kernel(GemmArgs g) {
             x = bias_bonus(x, g.sel_lam, pf_rb[it] + (int)((rbw >> (nn & 31)) & 1u));
           if constexpr (SAMPLE) x = sample_perturb(x, smp_inv_t, sample_noise(pf_seed[it], smp_step, nn));
           if (mask_eos && nn == g.sel_eos) x = -INFINITY;
+          if ((dnw >> (nn & 31)) & 1u) x = -INFINITY;   // (no rules: the word is 0)
           xi = nn;
         }
 #pragma unroll
@@ -1445,6 +1453,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_dec_kernel(GemmArgs g) {
 #pragma unroll
         for (int ks = 0; ks < KPW; ++ks) wn[d][ks] = wn[d + 1][ks];
       rbw = rbn;
+      dnw = dnn;
     } else {
       break;
     }
@@ -2491,6 +2500,8 @@ template <typename T>
 static void gemm_t(const GemmArgs& g, hipStream_t s) {
   if (g.sel_seeds && (!g.sel_val || g.tile || g.M > 64))
     throw std::runtime_error("internal error: sampling on a launch that is not the greedy LM head");
+  if ((g.sel_deny || g.sel_deny0) && (!g.sel_val || g.tile || g.M > 64))
+    throw std::runtime_error("internal error: token rules on a launch that is not the greedy LM head");
   if (g.tile) {   // decoder rows > 64 (beams, prefill): MFMA tiles, each weight tile read once per 64-128 rows
     if constexpr (sizeof(T) == 2) {
       // tile 2 (192+ rows, the d-wide and wide projections): 64-row tiles over a deep LDS-DMA ring, so

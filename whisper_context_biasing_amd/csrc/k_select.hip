@@ -27,6 +27,15 @@
 // token is a draw from softmax(score / T) (Gumbel-max). The finalize stays exact by the same argument: both
 // copies of a token carry the same noise g and x is monotone in score, so an underestimated copy never wins;
 // a masked EOS stays -inf. The log-prob of the chosen token is still its raw logit − logsumexp(raw logits).
+//
+// Token rules (SelectArgs::deny / deny0 / ts; tsrule.h): a denied token's candidate is -inf in every pass. With
+// the timestamp grammar on, the deny bitmaps cover [ts0, V) as well, so the partials and the re-scoring loops
+// yield the best allowed TEXT token (recomputed over [eos, ts0) from the logits in the one state whose text
+// range is that short); the finalize then scores the row's allowed timestamp range [lo, hi] from the logits
+// with lam·rowbase — a timestamp is a token no list names — reduces (max, Σexp) and the argmax in the fixed
+// lane-strided-then-butterfly order, and takes the best timestamp when logsumexp(timestamps) > max(text)
+// (rule 5: both sides carry the same log-softmax normaliser) or when it is the better candidate outright. A row
+// whose every candidate is -inf emits EOS. The log-prob of the chosen token stays raw logit − logsumexp(raw).
 #include <algorithm>
 
 #include "common.h"
@@ -57,6 +66,7 @@ __global__ __launch_bounds__(256) void select_partial_kernel(SelectArgs a) {
   const float* row = a.logits + (long)m * a.ld;
   const bool mask_eos = *a.step < a.min_new;
   const int rb = a.rowbase[m];
+  const uint32_t* deny = (a.deny0 && *a.step == 0) ? a.deny0 : a.deny;
   [[maybe_unused]] const int step = SAMPLE ? *a.step : 0;
   [[maybe_unused]] const float inv_t = SAMPLE ? *a.inv_t : 1.f;
   [[maybe_unused]] const uint64_t seed = SAMPLE ? a.seeds[m] : 0ull;
@@ -67,6 +77,7 @@ __global__ __launch_bounds__(256) void select_partial_kernel(SelectArgs a) {
     if (a.lam != 0.f) x = bias_bonus(x, a.lam, rb + (int)((a.root_bits[v >> 5] >> (v & 31)) & 1u));
     if constexpr (SAMPLE) x = sample_perturb(x, inv_t, sample_noise(seed, step, v));
     if (mask_eos && v == a.eos) x = -INFINITY;
+    if (deny && deny_bit(deny, v)) x = -INFINITY;
     if (better(x, v, bv, bi)) { bv = x; bi = v; }
   }
 #pragma unroll
@@ -111,6 +122,30 @@ __global__ __launch_bounds__(64) void select_finalize_kernel(SelectArgs a) {
   if (a.out_logprob) merge_lse_partials(a.part_max + (long)m * a.nchunk, a.part_sum + (long)m * a.nchunk, a.nchunk, lane, lm, ls);
   const int s = a.state[m];
   const int t0 = a.trans_off[s], t1 = a.trans_off[s + 1];
+  // token rules (wave-uniform; null / off: the step as it always was)
+  const uint32_t* deny = (a.deny0 && step == 0) ? a.deny0 : a.deny;
+  const bool ts_on = !SAMPLE && a.ts.on;
+  int text_lo = 0, w0 = 0, w1 = 0;
+  TsAllowed ta{0, 1, 0};
+  if (ts_on) {
+    w0 = a.ts_state[2 * m];
+    w1 = a.ts_state[2 * m + 1];
+    ta = ts_allowed(a.ts, a.V, a.eos, w0, w1);
+    text_lo = ta.text_lo;
+    if (text_lo > 0) {   // the partials hold the best of all text tokens: this state's text range is [text_lo, ts0)
+      const float* row = a.logits + (long)m * a.ld;
+      const int rb = a.rowbase[m];
+      bv = -INFINITY;
+      bi = 0x7fffffff;
+      for (int v = text_lo + lane; v < a.ts.ts0; v += 64) {
+        float x = row[v];
+        if (a.lam != 0.f) x = bias_bonus(x, a.lam, rb + (int)((a.root_bits[v >> 5] >> (v & 31)) & 1u));
+        if (mask_eos && v == a.eos) x = -INFINITY;
+        if (deny_bit(deny, v)) x = -INFINITY;
+        if (better(x, v, bv, bi)) { bv = x; bi = v; }
+      }
+    }
+  }
   if (a.lam != 0.f) {
     const float* row = a.logits + (long)m * a.ld;
     const int d = a.st_depth[s], k = a.st_keep[s];
@@ -122,6 +157,7 @@ __global__ __launch_bounds__(64) void select_finalize_kernel(SelectArgs a) {
       float x = bias_bonus(row[v], a.lam, d2 - d + min(k, d + 1 - d2));
       if constexpr (SAMPLE) x = sample_perturb(x, inv_t, sample_noise(seed, step, v));
       if (mask_eos && v == a.eos) x = -INFINITY;
+      if ((deny && deny_bit(deny, v)) || v < text_lo) x = -INFINITY;
       if (better(x, v, bv, bi)) { bv = x; bi = v; }
     }
     if constexpr (FOREST) {   // the clip's root children: n = k - d + 1 (the vocabulary pass gave them k - d)
@@ -130,6 +166,7 @@ __global__ __launch_bounds__(64) void select_finalize_kernel(SelectArgs a) {
         float x = bias_bonus(row[v], a.lam, k - d + 1);
         if constexpr (SAMPLE) x = sample_perturb(x, inv_t, sample_noise(seed, step, v));
         if (mask_eos && v == a.eos) x = -INFINITY;
+        if ((deny && deny_bit(deny, v)) || v < text_lo) x = -INFINITY;
         if (better(x, v, bv, bi)) { bv = x; bi = v; }
       }
     }
@@ -140,6 +177,29 @@ __global__ __launch_bounds__(64) void select_finalize_kernel(SelectArgs a) {
     const int oi = __shfl_xor(bi, o, 64);
     if (better(ov, oi, bv, bi)) { bv = ov; bi = oi; }   // (one token from both lists: the larger value stands)
   }
+  if (ts_on) {   // (bv, bi) is the best allowed text token; the allowed timestamps [lo, hi] from the logits
+    const float* row = a.logits + (long)m * a.ld;
+    const int rb = a.rowbase[m];
+    float tm = -INFINITY, tsum = 0.f, tv = -INFINITY;
+    int ti = 0x7fffffff;
+    for (int v = ta.lo + lane; v <= ta.hi; v += 64) {   // at most 1501 columns: 24 per lane
+      float x = row[v];
+      if (a.lam != 0.f) x = bias_bonus(x, a.lam, rb);
+      lse_push(tm, tsum, x);
+      if (better(x, v, tv, ti)) { tv = x; ti = v; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float om = __shfl_xor(tm, o, 64), os = __shfl_xor(tsum, o, 64);
+      lse_merge(tm, tsum, om, os);
+      const float ov = __shfl_xor(tv, o, 64);
+      const int oi = __shfl_xor(ti, o, 64);
+      if (better(ov, oi, tv, ti)) { tv = ov; ti = oi; }
+    }
+    const float lse_ts = tsum > 0.f ? tm + logf(tsum) : -INFINITY;
+    if (lse_ts > bv || better(tv, ti, bv, bi)) { bv = tv; bi = ti; }
+  }
+  if ((deny || ts_on) && !(bv > -INFINITY)) bi = 0x7fffffff;   // every candidate excluded: EOS (below)
   const bool fin = a.finished[m] != 0;
   // a row with no comparable value (all NaN) keeps bi = INT_MAX: emit EOS rather than an index past
   // the vocabulary (the next step's embedding lookup must stay in bounds)
@@ -207,6 +267,11 @@ __global__ __launch_bounds__(64) void select_finalize_kernel(SelectArgs a) {
     a.state[m] = dst;
     a.rowbase[m] = a.st_keep[dst] - a.st_depth[dst];
     a.next_ids[m] = tok;
+    if (ts_on && !fin) {   // finished rows keep their state
+      ts_advance(a.ts, tok, w0, w1);
+      a.ts_state[2 * m] = w0;
+      a.ts_state[2 * m + 1] = w1;
+    }
     a.out_ids[(long)m * a.out_ld + step] = tok;
     if (a.out_score) a.out_score[m] = fin ? 0.f : bv;
     if (a.out_logprob)   // the chosen token's raw logit against the row's logsumexp

@@ -4,6 +4,8 @@
 #include <hip/hip_ext.h>
 #include <stdint.h>
 
+#include "tsrule.h"
+
 namespace wcb {
 
 // Profiling pass only: while `start`/`stop` are set (runtime.cpp, wcb_handle::timed), every launch in
@@ -135,6 +137,11 @@ struct GemmArgs {
   // in the kernels' sampled instantiations; the softmax partials stay those of the raw logits. Both live in
   // a device buffer of the decode context, so a captured graph holds for every seed and temperature.
   const uint64_t* sel_seeds = nullptr; const float* sel_inv_t = nullptr;
+  // LM head, token rules (nullable, with sel_val; tsrule.h): deny bitmaps of vocab_pad / 32 words — a set bit makes
+  // the column's argmax candidate -inf (after the boost and the perturbation, beside the EOS mask; the softmax
+  // partials still take the raw value). sel_deny0, when non-null, replaces sel_deny at step 0 (*sel_step == 0).
+  // A run-time, wave-uniform null check: no instantiation of its own
+  const uint32_t* sel_deny = nullptr; const uint32_t* sel_deny0 = nullptr;
 };
 
 void gemm(DType t, const GemmArgs& g, hipStream_t s);
@@ -285,6 +292,13 @@ struct SelectArgs {
   // compared as perturbed scores, the re-scoring loops perturb their candidates alike, out_score receives the
   // winner's perturbed score; the log-prob stays raw logit − lse
   const uint64_t* seeds = nullptr; const float* inv_t = nullptr;
+  // token rules (tsrule.h). deny / deny0 (nullable): the LM head's bitmaps (deny0 at step 0), honoured by the
+  // vocabulary pass and the re-scoring loops. ts.on: the timestamp grammar — the partials then hold the best
+  // allowed TEXT token (the bitmaps have every bit of [ts0, V) set) and the finalize scores the allowed timestamp
+  // range from the logits itself; ts_state [M][2] is the row state (zero at the start of a decode). Greedy
+  // instantiations only: ts.on with seeds is refused by the runtime
+  const uint32_t* deny = nullptr; const uint32_t* deny0 = nullptr;
+  TsRule ts; int* ts_state = nullptr;
 };
 void select_greedy(const SelectArgs& a, hipStream_t s);          // vocabulary pass + finalize
 void select_finalize(const SelectArgs& a, hipStream_t s);        // partials already written (fused LM head)

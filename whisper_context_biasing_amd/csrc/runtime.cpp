@@ -177,9 +177,14 @@ struct DecCtx {
   DevBuf samp;
   hipGraphExec_t gexec_sm[2] = {}, gexec_k_sm[2] = {};
   std::string gkey_sm[2];
+  // token rules (wcb_set_token_rules): a ruled decode's own graphs beside the four kinds above ([0] plain, [1]
+  // with token log-probs, [2] / [3] sampled without / with them), so ruled and unruled calls each replay theirs
+  hipGraphExec_t gexec_tr[4] = {}, gexec_k_tr[4] = {};
+  std::string gkey_tr[4];
   void drop_graphs() {
     for (hipGraphExec_t* g : {&gexec, &gexec_k, &gexec_lp, &gexec_k_lp, &gexec_sm[0], &gexec_sm[1], &gexec_k_sm[0],
-                              &gexec_k_sm[1]}) {
+                              &gexec_k_sm[1], &gexec_tr[0], &gexec_tr[1], &gexec_tr[2], &gexec_tr[3], &gexec_k_tr[0],
+                              &gexec_k_tr[1], &gexec_k_tr[2], &gexec_k_tr[3]}) {
       if (*g) (void)hipGraphExecDestroy(*g);
       *g = nullptr;
     }
@@ -187,8 +192,11 @@ struct DecCtx {
     gkey_lp.clear();
     gkey_sm[0].clear();
     gkey_sm[1].clear();
+    for (std::string& k : gkey_tr) k.clear();
   }
-  std::string all_gkeys() const { return gkey + gkey_lp + gkey_sm[0] + gkey_sm[1]; }
+  std::string all_gkeys() const {
+    return gkey + gkey_lp + gkey_sm[0] + gkey_sm[1] + gkey_tr[0] + gkey_tr[1] + gkey_tr[2] + gkey_tr[3];
+  }
   // per-utterance bias forest of the call decoding in this context: device buffer carved by the capacities
   // (states, transitions, root children; they only grow: quiesce + realloc, the graph key names them), the
   // pinned staging copy the asynchronous upload reads, and the event of the last upload from it
@@ -344,6 +352,11 @@ struct wcb_handle {
   int lean_x = 1;
   int64_t n_graph_captures = 0;   // decode graphs instantiated so far (wcb_debug_counter "graph_captures")
   struct wcb_state* step_state = nullptr;   // the active step-wise decode (wcb_decode_begin), if any
+  // token rules (wcb_set_token_rules): the deny bitmaps [vocab_pad / 32] of every step and of step 0, allocated by
+  // the first call and never moved (the ruled graphs hold their addresses); deny0 is read only when has0
+  bool rules_on = false, rules_has0 = false;
+  TsRule rules_ts;
+  DevBuf rules_deny, rules_deny0;
   // encoder GEMM tile order (option "enc_raster"): bands of n row panels with the column tiles outer
   // (GemmArgs::raster; 0 = row-major). 8 measured best with the round-3 ring kernel (whisper-small:
   // QKV 185 -> 177, fc1 297 -> 281, out 118 -> 116 us, fc2 within noise; profiles/r03f_enc_gemm_bench.txt)
@@ -685,7 +698,8 @@ void wcb_destroy(wcb_handle* h) {
   }
   for (auto& b : h->owned) b.release();
   for (DevBuf* b : {&h->dft, &h->dft3, &h->mel_lo, &h->mel_hi, &h->mel_w, &h->clip_max, &h->xt, &h->hbuf, &h->x, &h->h,
-                    &h->qkv, &h->att, &h->ffn, &h->encout, &h->stamps, &h->stamp_acc, &h->dev_err})
+                    &h->qkv, &h->att, &h->ffn, &h->encout, &h->stamps, &h->stamp_acc, &h->dev_err, &h->rules_deny,
+                    &h->rules_deny0})
     b->release();
   for (auto e : h->ev_pool) (void)hipEventDestroy(e);
   if (h->ev_in) (void)hipEventDestroy(h->ev_in);
@@ -1241,7 +1255,7 @@ void ensure_dec_ws(wcb_handle* h, int clips, int B, int T, int out_ld, int xmode
   const DecCtx& D0 = h->dc[c1 - 1];   // every context of the range is sized together
   const size_t xbuf = xmode ? (size_t)xenc_fm_elems(clips, (int)S, (int)d) * e : 2 * L * (size_t)clips * S * d * e;
   const size_t need[] = {xbuf, 2 * L * (size_t)B * T * d * e, (size_t)rows * d * 4,
-                         (size_t)rows * h->d.ffn * e, (size_t)B * h->vocab_pad * 4, (size_t)(I_NEXT + 4 * B + 16) * 4,
+                         (size_t)rows * h->d.ffn * e, (size_t)B * h->vocab_pad * 4, (size_t)(I_NEXT + 6 * B + 16) * 4,
                          (size_t)B * out_ld * 4};
   const DevBuf* have[] = {&h->xkv2[c1 - 1], &D0.kvself, &D0.dx, &D0.dffn, &D0.logits, &D0.ints, &D0.outbuf};
   bool grow = false;
@@ -1339,7 +1353,19 @@ struct StepCfg {
   // greedy select, temperature sampling: the context's samp words (inv_T, then the seed of every row). Null:
   // the step as it always was
   const uint64_t* samp = nullptr;
+  // greedy select, token rules (the handle's; null / off: the step as it always was): the deny bitmaps of the LM
+  // head and the finalize, the timestamp grammar of the finalize (row state: two ints per row behind rowbase)
+  const uint32_t* deny = nullptr; const uint32_t* deny0 = nullptr;
+  TsRule ts;
 };
+
+// the handle's token rules into a greedy step configuration
+void apply_rules(const wcb_handle* h, StepCfg& c) {
+  if (!h->rules_on) return;
+  c.deny = h->rules_deny.as<uint32_t>();
+  c.deny0 = h->rules_has0 ? h->rules_deny0.as<uint32_t>() : nullptr;
+  c.ts = h->rules_ts;
+}
 
 // the residual's fragment-major copy applies (lean path): the lean LayerNorm table covers d, every
 // LN consumer and residual writer has its weights' fragment-major copy, and the decode GEMMs publish
@@ -1619,6 +1645,7 @@ void decode_rows(wcb_handle* h, const StepCfg& c, int b0, int nb, int chain, hip
         lm.sel_inv_t = reinterpret_cast<const float*>(c.samp);
         lm.sel_seeds = c.samp + 1 + b0;
       }
+      lm.sel_deny = c.deny; lm.sel_deny0 = c.deny0;   // token rules (null: none)
     }
     if (lm_tiled) {
       proj("lm_head", lm);
@@ -1698,6 +1725,7 @@ void decode_step(wcb_handle* h, const StepCfg& c) {
       s.part_max = D.part_max.as<float>(); s.part_sum = D.part_sum.as<float>(); s.out_logprob = c.logprob_out;
     }
     if (c.samp) { s.inv_t = reinterpret_cast<const float*>(c.samp); s.seeds = c.samp + 1; }
+    s.deny = c.deny; s.deny0 = c.deny0; s.ts = c.ts; s.ts_state = next_ids + 4 * B;
     if (c.embedded) {   // the next step's input embedding in the same launch (embed()'s outputs)
       const bool r32 = h->dec_gemm && lnf_possible(h);
       s.emb = h->tok_emb; s.pemb = h->dec_pos; s.n_pos = h->d.n_text_ctx; s.d = d; s.dtype = h->dt;
@@ -1926,6 +1954,10 @@ static void generate_impl(wcb_handle* h, const float* mel, int B, const wcb_gen_
       check_sampling(smp->temperature, smp->seeds);
       if (nb > 1) throw WcbError(WCB_ERR_UNSUPPORTED, "sampling is greedy only (num_beams = 1)");
     }
+    if (h->rules_on && nb > 1)
+      throw WcbError(WCB_ERR_UNSUPPORTED, "token rules are greedy only (num_beams = 1; wcb_set_token_rules(h, NULL) removes them)");
+    if (h->rules_on && h->rules_ts.on && smp)
+      throw WcbError(WCB_ERR_UNSUPPORTED, "timestamp decoding with sampling is not supported (greedy only)");
     if (nb > 1 && out_logprobs)
       throw WcbError(WCB_ERR_UNSUPPORTED, "token log-probs are greedy only (beam search: out_seq_scores)");
     if (nb == 1 && out_seq_scores)
@@ -1978,7 +2010,7 @@ static void generate_impl(wcb_handle* h, const float* mel, int B, const wcb_gen_
     // ---- decode stream
     HIPCHK(hipStreamWaitEvent(D.hs, h->ev_xkv[buf], 0));
     int* ints = D.ints.as<int>();
-    HIPCHK(hipMemsetAsync(ints, 0, (size_t)(I_NEXT + 4 * R) * 4, D.hs));
+    HIPCHK(hipMemsetAsync(ints, 0, (size_t)(I_NEXT + 6 * R) * 4, D.hs));   // (the rule state with finished[])
     if (prefix) {   // one prefix row shared by every decoder row (forced_ld = 0 below)
       if ((size_t)P * 4 > D.forced.bytes) { quiesce(h); D.forced.ensure((size_t)P * 4); }
       write_i32(D.forced.as<int>(), prefix, P, D.hs);
@@ -2009,6 +2041,8 @@ static void generate_impl(wcb_handle* h, const float* mel, int B, const wcb_gen_
       HIPCHK(hipMemsetAsync(D.lpbuf.p, 0, (size_t)R * out_ld * 4, D.hs));
     }
     if (smp) sc.samp = install_sampling(D, smp->temperature, smp->seeds, R);
+    const bool ruled = nb == 1 && h->rules_on;
+    if (ruled) apply_rules(h, sc);
     // prompt positions 0 .. P-2 in causal prefill passes, then the last prompt token is the first
     // decode step's input
     for (int p0 = 0, np; p0 + 1 < P; p0 += np) {
@@ -2027,8 +2061,10 @@ static void generate_impl(wcb_handle* h, const float* mel, int B, const wcb_gen_
     char key[256], bkey[64];
     if (bb) snprintf(bkey, sizeof bkey, "F%d.%d.%d", D.f_ns, D.f_nt, D.f_nrc);
     else snprintf(bkey, sizeof bkey, "%llu", (unsigned long long)bs->id);
-    snprintf(key, sizeof key, "%d/%d/%d/%d/%s/%a/%d/%d/%d/%d", B, nb, Tc, out_ld, bkey,
-             cfg->bias_boost, cfg->min_new_tokens, h->n_sub, (int)h->prof_stamps, P);
+    int kn = snprintf(key, sizeof key, "%d/%d/%d/%d/%s/%a/%d/%d/%d/%d", B, nb, Tc, out_ld, bkey,
+                      cfg->bias_boost, cfg->min_new_tokens, h->n_sub, (int)h->prof_stamps, P);
+    if (ruled)   // what a ruled graph bakes in beside the bitmaps' stable addresses
+      snprintf(key + kn, sizeof key - kn, "/R%d.%d.%d.%d", sc.ts.on, sc.ts.ts0, sc.ts.max_init, (int)h->rules_has0);
     const int max_new = cfg->max_new_tokens;
     // per-launch HIP events (profiling bit 0) cannot bracket nodes of a replayed graph: eager launches
     const bool use_graph = cfg->use_graph && !h->prof;
@@ -2041,9 +2077,10 @@ static void generate_impl(wcb_handle* h, const float* mel, int B, const wcb_gen_
     // (a scored decode has its own graphs and key: neither kind of call evicts the other's; so has a sampled
     // one, without and with log-probs — its key is the same string: never the seeds or the temperature)
     const int lpi = out_logprobs ? 1 : 0;
-    hipGraphExec_t& gexec = smp ? D.gexec_sm[lpi] : out_logprobs ? D.gexec_lp : D.gexec;
-    hipGraphExec_t& gexec_k = smp ? D.gexec_k_sm[lpi] : out_logprobs ? D.gexec_k_lp : D.gexec_k;
-    std::string& gkey = smp ? D.gkey_sm[lpi] : out_logprobs ? D.gkey_lp : D.gkey;
+    const int tri = (smp ? 2 : 0) + lpi;   // a ruled decode: its own four kinds
+    hipGraphExec_t& gexec = ruled ? D.gexec_tr[tri] : smp ? D.gexec_sm[lpi] : out_logprobs ? D.gexec_lp : D.gexec;
+    hipGraphExec_t& gexec_k = ruled ? D.gexec_k_tr[tri] : smp ? D.gexec_k_sm[lpi] : out_logprobs ? D.gexec_k_lp : D.gexec_k;
+    std::string& gkey = ruled ? D.gkey_tr[tri] : smp ? D.gkey_sm[lpi] : out_logprobs ? D.gkey_lp : D.gkey;
     if (use_graph && (!gexec || gkey != key)) {
       if (gexec) { (void)hipGraphExecDestroy(gexec); gexec = nullptr; }
       if (gexec_k) { (void)hipGraphExecDestroy(gexec_k); gexec_k = nullptr; }
@@ -2197,6 +2234,8 @@ static void decode_begin_beams(wcb_handle* h, const void* enc, int B, int nb, co
   REQUIRE(h && enc && out && B > 0 && B <= 64, "bad argument (1 <= B <= 64, enc and out required)");
   if (!h->ready) throw WcbError(WCB_ERR_STATE, "weights not finalized");
   REQUIRE(nb >= 2 && nb <= kMaxBeams, "num_beams must be in [2, 8] (greedy: num_beams = 1)");
+  if (h->rules_on)
+    throw WcbError(WCB_ERR_UNSUPPORTED, "token rules are greedy only (num_beams = 1; wcb_set_token_rules(h, NULL) removes them)");
   const int R = B * nb;
   REQUIRE(R <= 64 * DecCtx::kMaxSub, "batch x num_beams > 512 rows: split the batch");
   REQUIRE(h->nctx < wcb_handle::kMaxCtx, "step-wise decoding needs a free decode context (decode_contexts <= 3)");
@@ -2286,7 +2325,7 @@ int wcb_decode_begin(wcb_handle* h, const void* enc, int B, int num_beams, const
       HIPCHK(hipStreamSynchronize(h->he));
     }
     int* ints = D.ints.as<int>();
-    HIPCHK(hipMemsetAsync(ints, 0, (size_t)(I_NEXT + 4 * B) * 4, D.hs));
+    HIPCHK(hipMemsetAsync(ints, 0, (size_t)(I_NEXT + 6 * B) * 4, D.hs));   // (the rule state with finished[])
     if (prefix) {   // per-row prefixes [B][P] (host), positions 0 .. P-2 prefilled, P-1 is the first input
       if ((size_t)B * P * 4 > D.forced.bytes) { quiesce(h); D.forced.ensure((size_t)B * P * 4); }
       HIPCHK(hipMemcpyAsync(D.forced.p, prefix, (size_t)B * P * 4, hipMemcpyHostToDevice, D.hs));
@@ -2356,6 +2395,7 @@ int wcb_decode_step(wcb_handle* h, wcb_state* st, const wcb_bias* bias, int32_t*
       sc.embedded = true;   // (wcb_decode_begin embedded the first input; each finalize embeds the next)
       if (st->logprobs) sc.logprob_out = D.lpbuf.as<float>();
       if (st->sampling) sc.samp = D.samp.as<uint64_t>();
+      apply_rules(h, sc);   // (fixed for the whole decode: wcb_set_token_rules is refused while the state is open)
     }
     if (st->forest) sc.forest = &st->fd;
     decode_step(h, sc);
@@ -2464,6 +2504,8 @@ int wcb_decode_enable_sampling(wcb_handle* h, wcb_state* st, float temperature, 
     REQUIRE(h && st && st->h == h && h->step_state == st, "bad argument (state of this handle)");
     check_sampling(temperature, seeds);
     if (st->nb > 1) throw WcbError(WCB_ERR_UNSUPPORTED, "sampling is greedy only (a beam-search state)");
+    if (h->rules_on && h->rules_ts.on)
+      throw WcbError(WCB_ERR_UNSUPPORTED, "timestamp decoding with sampling is not supported (greedy only)");
     if (st->fwd != 0) throw WcbError(WCB_ERR_STATE, "wcb_decode_enable_sampling on a forward cache (wcb_forward_cached state)");
     if (st->steps != 0) throw WcbError(WCB_ERR_STATE, "wcb_decode_enable_sampling: after the first step (right after wcb_decode_begin)");
     install_sampling(h->dc[wcb_handle::kMaxCtx - 1], temperature, seeds, st->B);
@@ -3009,6 +3051,201 @@ int wcb_sample_noise(uint64_t seed, int step, int v0, int n, float* out) {
   return guarded(nullptr, [&] {
     REQUIRE(out && n >= 0 && step >= 0 && v0 >= 0 && (long)v0 + n <= 0x7fffffffL, "bad argument (out, n, step, v0 >= 0)");
     for (int i = 0; i < n; ++i) out[i] = sample_noise(seed, step, v0 + i);
+  });
+}
+
+// ---- token rules (wcb.h wcb_token_rules; csrc/tsrule.h)
+extern "C++" {
+namespace {
+
+void check_rules(const wcb_token_rules* r, int V, int eos) {
+  REQUIRE(r->n_suppress >= 0 && r->n_begin_suppress >= 0, "token rules: negative list length");
+  REQUIRE((r->n_suppress == 0 || r->suppress) && (r->n_begin_suppress == 0 || r->begin_suppress), "token rules: null id list");
+  REQUIRE(r->timestamps == 0 || r->timestamps == 1, "token rules: timestamps must be 0 or 1");
+  const int lim = r->timestamps ? r->timestamp_begin : V;
+  if (r->timestamps) {
+    REQUIRE(r->timestamp_begin > eos && r->timestamp_begin < V, "token rules: timestamp_begin must lie in (eos, vocab)");
+    REQUIRE(r->no_timestamps_token_id >= 0 && r->no_timestamps_token_id < r->timestamp_begin,
+            "token rules: no_timestamps_token_id must lie in [0, timestamp_begin)");
+  }
+  for (int i = 0; i < r->n_suppress; ++i)
+    REQUIRE(r->suppress[i] >= 0 && r->suppress[i] < V && r->suppress[i] < lim,
+            "token rules: suppress id outside [0, vocab) (with timestamps: [0, timestamp_begin))");
+  for (int i = 0; i < r->n_begin_suppress; ++i)
+    REQUIRE(r->begin_suppress[i] >= 0 && r->begin_suppress[i] < V && r->begin_suppress[i] < lim,
+            "token rules: begin_suppress id outside [0, vocab) (with timestamps: [0, timestamp_begin))");
+}
+
+TsRule rules_ts(const wcb_token_rules* r) {
+  TsRule t;
+  t.on = r->timestamps;
+  t.ts0 = r->timestamps ? r->timestamp_begin : 0;
+  t.max_init = r->max_initial_timestamp_index < 0 ? -1 : r->max_initial_timestamp_index;
+  return t;
+}
+
+// the deny bitmaps of every step (d) and of step 0 (d0), `words` 32-bit words each: the suppress ids, at step 0
+// the begin_suppress ids too; with the timestamp grammar no_timestamps and every id of [timestamp_begin, V) — the
+// LM head's winner is then the best allowed text token, the finalize scores the timestamps itself
+void build_deny(const wcb_token_rules* r, int V, size_t words, std::vector<uint32_t>& d, std::vector<uint32_t>& d0) {
+  d.assign(words, 0u);
+  auto set = [](std::vector<uint32_t>& b, int v) { b[(size_t)v >> 5] |= 1u << (v & 31); };
+  for (int i = 0; i < r->n_suppress; ++i) set(d, r->suppress[i]);
+  if (r->timestamps) {
+    set(d, r->no_timestamps_token_id);
+    for (int v = r->timestamp_begin; v < V; ++v) set(d, v);
+  }
+  d0 = d;
+  for (int i = 0; i < r->n_begin_suppress; ++i) set(d0, r->begin_suppress[i]);
+}
+
+}  // namespace
+}  // extern "C++"
+
+int wcb_set_token_rules(wcb_handle* h, const wcb_token_rules* r) {
+  return guarded(h, [&] {
+    REQUIRE(h, "null handle");
+    if (!h->ready) throw WcbError(WCB_ERR_STATE, "weights not finalized");
+    if (h->step_state) throw WcbError(WCB_ERR_STATE, "wcb_set_token_rules: a step-wise decode is active (wcb_decode_end first)");
+    if (!r) { h->rules_on = false; return; }
+    check_rules(r, h->d.vocab, h->d.eos_token_id);
+    const size_t words = (size_t)h->vocab_pad / 32;
+    std::vector<uint32_t> d, d0;
+    build_deny(r, h->d.vocab, words, d, d0);
+    quiesce(h);   // queued decodes read the bitmaps
+    h->rules_deny.ensure(words * 4);    // (allocated once: vocab_pad is fixed by the weights)
+    h->rules_deny0.ensure(words * 4);
+    HIPCHK(hipMemcpy(h->rules_deny.p, d.data(), words * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->rules_deny0.p, d0.data(), words * 4, hipMemcpyHostToDevice));
+    h->rules_has0 = r->n_begin_suppress > 0;
+    h->rules_ts = rules_ts(r);
+    h->rules_on = true;
+  });
+}
+
+int wcb_token_rules_apply_host(const wcb_token_rules* r, int vocab, int eos, const int32_t* generated, int n, float* scores) {
+  return guarded(nullptr, [&] {
+    REQUIRE(r && scores && vocab > 0 && eos >= 0 && eos < vocab && n >= 0 && (n == 0 || generated), "bad argument");
+    check_rules(r, vocab, eos);
+    const size_t words = ((size_t)vocab + 127) / 128 * 4;
+    std::vector<uint32_t> d, d0;
+    build_deny(r, vocab, words, d, d0);
+    const TsRule ts = rules_ts(r);
+    const uint32_t* deny = n == 0 ? d0.data() : d.data();
+    if (!ts.on) {
+      for (int v = 0; v < vocab; ++v)
+        if (deny_bit(deny, v)) scores[v] = -INFINITY;
+      return;
+    }
+    int w0 = 0, w1 = 0;
+    for (int i = 0; i < n; ++i) {
+      REQUIRE(generated[i] >= 0 && generated[i] < vocab, "generated id outside [0, vocab)");
+      ts_advance(ts, generated[i], w0, w1);
+    }
+    const TsAllowed a = ts_allowed(ts, vocab, eos, w0, w1);
+    double tmax = -INFINITY, xmax = -INFINITY;
+    for (int v = 0; v < ts.ts0; ++v) {
+      if (v < a.text_lo || deny_bit(deny, v)) scores[v] = -INFINITY;
+      xmax = std::max(xmax, (double)scores[v]);
+    }
+    for (int v = ts.ts0; v < vocab; ++v) {
+      if (v < a.lo || v > a.hi) scores[v] = -INFINITY;
+      tmax = std::max(tmax, (double)scores[v]);
+    }
+    double sum = 0.0;
+    if (tmax > -INFINITY)
+      for (int v = a.lo; v <= a.hi; ++v) sum += std::exp((double)scores[v] - tmax);
+    const double lse = sum > 0.0 ? tmax + std::log(sum) : -INFINITY;
+    if (lse > xmax)   // rule 5: the timestamps together outweigh the best text token
+      for (int v = 0; v < ts.ts0; ++v) scores[v] = -INFINITY;
+  });
+}
+
+int wcb_op_lm_head_rules(int dtype, const void* A, const void* W, int M, int V, int K, int walkers,
+                         const wcb_token_rules* rules, int eos, const int32_t* generated, int gen_ld, const int32_t* lens,
+                         float* logits, long ld, int32_t* next_ids, void* stream) {
+  return guarded(nullptr, [&] {
+    REQUIRE(A && W && logits && next_ids && rules && lens && M > 0 && M <= 64 && V > 0 && K > 0 && ld >= V && eos >= 0 && eos < V,
+            "bad argument (1 <= M <= 64, ld >= V, 0 <= eos < V, every pointer)");
+    REQUIRE(dtype >= WCB_BF16 && dtype <= WCB_F32, "dtype");
+    REQUIRE(walkers >= 0 && walkers <= 4096, "walkers: 0 (default) .. 4096");
+    check_rules(rules, V, eos);
+    const DType dt = DType(dtype);
+    if (!gemm_dec_supported(dt, K) && K != 32 && K != 2560)
+      throw WcbError(WCB_ERR_UNSUPPORTED, "K: 64, 128, 256, 384, 512, 768, 1024, 1280 (column walk) or 32, 2560 (skinny kernel)");
+    const TsRule ts = rules_ts(rules);
+    // the row states after their histories; the launch's step: 0 when every row is at t == 0
+    std::vector<int> host((size_t)2 * M, 0);
+    int n0 = 0;
+    for (int m = 0; m < M; ++m) {
+      REQUIRE(lens[m] >= 0 && (lens[m] == 0 || (generated && gen_ld >= lens[m])), "lens / generated");
+      n0 += lens[m] == 0;
+      int w0 = 0, w1 = 0;
+      for (int i = 0; i < lens[m]; ++i) {
+        const int tok = generated[(size_t)m * gen_ld + i];
+        REQUIRE(tok >= 0 && tok < V, "generated id outside [0, vocab)");
+        ts_advance(ts, tok, w0, w1);
+      }
+      host[2 * m] = w0;
+      host[2 * m + 1] = w1;
+    }
+    REQUIRE(ts.on || rules->n_begin_suppress == 0 || n0 == 0 || n0 == M,
+            "rows at t == 0 and t > 0 in one call with begin_suppress ids (the bitmap of a launch is chosen by its step)");
+    hipStream_t st = (hipStream_t)stream;
+    const int wk = walkers > 0 ? walkers : kDecWalkers;
+    const int nchunk = lm_head_partials(dt, K, V, wk);
+    struct Scratch { DevBuf b; ~Scratch() { b.release(); } } pv, pi, zi, bm, wpad, wfm;
+    const size_t np = (size_t)M * nchunk * 4, words = ((size_t)V + 127) / 128 * 4;
+    pv.b.ensure(np); pi.b.ensure(np);
+    std::vector<uint32_t> d, d0;
+    build_deny(rules, V, words, d, d0);
+    bm.b.ensure(2 * words * 4);
+    HIPCHK(hipMemcpyAsync(bm.b.p, d.data(), words * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(bm.b.as<uint32_t>() + words, d0.data(), words * 4, hipMemcpyHostToDevice, st));
+    // one zeroed int block: the counters, then the per-row arrays of a one-step decode with an empty forest
+    // (every row in root state 0, no transitions, no root children), the rule states and the id column
+    int* z = nullptr;
+    const size_t zn = 16 + (size_t)10 * M + 8;
+    zi.b.ensure(zn * 4);
+    z = zi.b.as<int>();
+    int* zstate = z + 16;
+    int* zts = z + 16 + 6 * M + 8;
+    int* zout = zts + 2 * M;
+    const int step0 = n0 == M ? 0 : 1;
+    write_i32(z, &step0, 1, st);
+    write_i32(zts, host.data(), 2 * M, st);
+    GemmArgs lm = drow(A, K, W, M, V, K, logits, ld);
+    lm.out_f32 = 1;
+    lm.walkers = wk;
+    lm.sel_val = pv.b.as<float>(); lm.sel_idx = pi.b.as<int>();
+    lm.sel_step = z;   // min_new 0: no EOS mask; lam 0: no boost
+    lm.sel_deny = bm.b.as<uint32_t>();
+    lm.sel_deny0 = rules->n_begin_suppress > 0 ? bm.b.as<uint32_t>() + words : nullptr;
+    int nw = 0, kpw = 0;
+    if (dt != kF32 && gemm_dec_supported(dt, K) && lean_cfg(K, nw, kpw)) {   // as op_lm_head: fragment-major weights
+      const size_t e = esize(dtype), vp = (size_t)(V + 15) / 16 * 16;
+      wpad.b.ensure(vp * K * e);
+      wfm.b.ensure(vp * K * e);
+      HIPCHK(hipMemcpyAsync(wpad.b.p, W, (size_t)V * K * e, hipMemcpyDeviceToDevice, st));
+      frag_major(dt, wpad.b.p, (int)vp, K, nw, kpw, wfm.b.p, st);
+      lm.W_fm = wfm.b.p;
+    }
+    gemm(dt, lm, st);
+    SelectArgs s;
+    s.logits = logits; s.ld = ld; s.M = M; s.V = V;
+    s.trans_off = zstate + 5 * M + 2; s.trans_tok = nullptr; s.trans_dst = nullptr;
+    s.st_depth = zstate + 5 * M + 4; s.st_keep = zstate + 5 * M + 5;
+    s.state = zstate; s.finished = zstate + M; s.rowbase = zstate + 2 * M;
+    s.forest.root = zstate + 3 * M; s.forest.rc_off = zstate + 4 * M;   // [M + 1] zeros
+    s.eos = eos; s.pad = eos; s.min_new = 0;
+    s.step = z; s.pos = z + 1; s.all_done = z + 2;
+    s.ticket_unfin = reinterpret_cast<unsigned long long*>(z + 4);
+    s.next_ids = next_ids; s.out_ids = zout; s.out_ld = 2;
+    s.part_val = lm.sel_val; s.part_idx = lm.sel_idx; s.nchunk = nchunk;
+    s.deny = lm.sel_deny; s.deny0 = lm.sel_deny0; s.ts = ts; s.ts_state = zts;
+    select_finalize(s, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));   // the scratch buffers and the pageable host sources live until here
   });
 }
 

@@ -31,7 +31,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .config import N_SAMPLES, WhisperDims, dims_from_hf_config, get_dims
+from .config import N_SAMPLES, TIME_PRECISION, WhisperDims, dims_from_hf_config, get_dims, parse_segments, timestamp_ids
 
 _TORCH_DT = {_lib.WCB_BF16: torch.bfloat16, _lib.WCB_F16: torch.float16, _lib.WCB_F32: torch.float32}
 
@@ -94,6 +94,9 @@ class GenerateOutput:
     sequences_scores: Optional[torch.Tensor] = None
     # generate(temperature=(t0, t1, ...)): the temperature each clip's result was decoded at, [B] f32
     temperatures: Optional[torch.Tensor] = None
+    # generate(return_timestamps=True): per clip a list of (start_s, end_s, token_ids) parsed on the host from the
+    # generated ids (config.parse_segments); end_s None for a trailing segment without a closing timestamp
+    segments: Optional[list] = None
 
 
 @dataclass
@@ -327,6 +330,7 @@ class WhisperCB:
         # asynchronous (block=False) generate call. Past kRetiredMax they are released anyway (one stall).
         self._bias_retired: List[BiasList] = []
         self._word_start: Optional[np.ndarray] = None
+        self._rules_key = None   # the token rules installed on the handle (wcb_set_token_rules), None: none
         self._loaded = False
         self._cache: Optional["DecoderCache"] = None   # the open forward(use_cache=True) state, if any
         # options last: a rejected option raises with every attribute __del__ reads already set
@@ -516,13 +520,59 @@ class WhisperCB:
         return lists
 
     # ---------------------------------------------------------------------------- generation
+    def _rules_key_of(self, return_timestamps, suppress_tokens, begin_suppress_tokens, max_initial_timestamp):
+        """The token rules the four generate() / decode_begin() arguments ask for, as a hashable key (None: none)."""
+        sup = tuple(sorted({int(t) for t in (suppress_tokens or ())}))
+        beg = tuple(sorted({int(t) for t in (begin_suppress_tokens or ())}))
+        ts = bool(return_timestamps)
+        for t in sup + beg:
+            if not 0 <= t < self.dims.vocab:
+                raise ValueError(f"suppress id {t} outside [0, {self.dims.vocab})")
+        mi = -1
+        if max_initial_timestamp is not None:
+            if not ts:
+                raise ValueError("max_initial_timestamp needs return_timestamps=True")
+            if not (float(max_initial_timestamp) >= 0.0 and math.isfinite(float(max_initial_timestamp))):
+                raise ValueError(f"max_initial_timestamp must be finite and >= 0, got {max_initial_timestamp!r}")
+            mi = int(round(float(max_initial_timestamp) / TIME_PRECISION))
+        if not (ts or sup or beg):
+            return None
+        if ts:
+            ts0 = timestamp_ids(self.dims)[0]
+            if ts0 <= self.dims.eos_token_id:
+                raise ValueError("this vocabulary has no timestamp tokens past EOS")
+            bad = [t for t in sup + beg if t >= ts0]
+            if bad:
+                raise ValueError(f"suppress ids {bad} are timestamp tokens (>= {ts0}): the grammar decides those")
+        return (sup, beg, ts, mi)
+
+    def _install_rules(self, key) -> None:
+        """Make `key` the handle's token rules (handle state, like a generation config; a no-op when it already is)."""
+        if key == self._rules_key:
+            return
+        if key is None:
+            _lib.check(self._lib.wcb_set_token_rules(self._h, None), self._h, "wcb_set_token_rules")
+        else:
+            sup, beg, ts, mi = key
+            ts0, nots = timestamp_ids(self.dims)
+            r, keep = _lib.token_rules(sup, beg, ts, ts0, nots, mi)
+            _lib.check(self._lib.wcb_set_token_rules(self._h, C.byref(r)), self._h, "wcb_set_token_rules")
+            del keep
+        self._rules_key = key
+
+    def _segments(self, ids) -> list:
+        ts0 = timestamp_ids(self.dims)[0]
+        return [parse_segments(row, ts0, self.dims.eos_token_id) for row in np.asarray(ids)]
+
     def generate(self, input_features=None, labels=None, bias_spans=None, max_length: Optional[int] = None,
                  num_beams: Optional[int] = None, bias_list=None, bias_boost: float = 0.0,
                  min_new_tokens: int = 0, prompt_ids=None, return_dict_in_generate: bool = False,
                  generation_config=None, use_graph: bool = True, block: bool = True, bias_lists=None,
                  per_utterance_bias: bool = False, output_logprobs: bool = False, temperature=0.0, seed=0,
                  do_sample: Optional[bool] = None, logprob_threshold: Optional[float] = -1.0,
-                 compression_ratio_threshold: Optional[float] = 2.4, **kwargs):
+                 compression_ratio_threshold: Optional[float] = 2.4, return_timestamps: bool = False,
+                 suppress_tokens=None, begin_suppress_tokens=None, max_initial_timestamp: Optional[float] = None,
+                 **kwargs):
         """Greedy (num_beams = 1, the reference's eval setting) or HF beam
         search (num_beams = 2..8, [tf] generation/utils.py:3208) on the device.
 
@@ -565,11 +615,32 @@ class WhisperCB:
         that result, one that fails at the last temperature keeps the last. An int seed gives attempt i
         `clip_seeds(seed, 0, B, attempt=i)`, explicit per-clip seeds s_b give s_b + i·0x9E3779B97F4A7C15 (mod
         2^64). Returns a GenerateOutput with `temperatures` [B]. Failing clips are re-encoded from their mel.
+
+        Token rules, applied on the device at every greedy step (wcb_set_token_rules; all off by default, and
+        `config.suppress_tokens` is not read): `suppress_tokens=[...]` are never generated,
+        `begin_suppress_tokens=[...]` not as the first token. `return_timestamps=True` decodes with Whisper's
+        timestamp grammar (HF WhisperTimeStampLogitsProcessor: drive it from a prompt without <|notimestamps|>)
+        and returns a GenerateOutput whose `segments` holds per clip a list of (start_s, end_s, token_ids);
+        `max_initial_timestamp=1.0` (seconds) bounds the first timestamp. Greedy only: with `num_beams > 1`, and
+        for timestamps also with `temperature > 0` or a temperature sequence, the call raises ValueError.
         """
         if not self._loaded:
             raise _lib.WcbError("weights not loaded")
-        if output_logprobs:
+        if output_logprobs or return_timestamps:
             return_dict_in_generate = True
+        rules_kw = dict(return_timestamps=return_timestamps, suppress_tokens=suppress_tokens,
+                        begin_suppress_tokens=begin_suppress_tokens, max_initial_timestamp=max_initial_timestamp)
+        rules = self._rules_key_of(**rules_kw)
+        if rules is not None:   # what the library refuses, before any work
+            nb_rules = int(num_beams if num_beams is not None else getattr(generation_config or self.generation_config,
+                                                                            "num_beams", 1) or 1)
+            if nb_rules != 1:
+                raise ValueError("suppress_tokens / begin_suppress_tokens / return_timestamps are greedy only: num_beams must be 1")
+            if return_timestamps and (isinstance(temperature, (list, tuple, np.ndarray)) or do_sample
+                                      or (do_sample is not False and float(temperature) > 0.0)):
+                raise ValueError("return_timestamps with sampling or a temperature fallback is not supported")
+            if return_timestamps and not block:
+                raise ValueError("return_timestamps parses the ids on the host: block=False is not supported")
         x_all = self._features(input_features)
         if isinstance(temperature, (list, tuple, np.ndarray)):
             if not block:
@@ -579,7 +650,7 @@ class WhisperCB:
                 dict(labels=labels, bias_spans=bias_spans, max_length=max_length, num_beams=num_beams, bias_list=bias_list,
                      bias_boost=bias_boost, min_new_tokens=min_new_tokens, prompt_ids=prompt_ids,
                      generation_config=generation_config, use_graph=use_graph, bias_lists=bias_lists,
-                     per_utterance_bias=per_utterance_bias))
+                     per_utterance_bias=per_utterance_bias, **rules_kw))
         T = float(temperature)
         if do_sample and T == 0.0:
             T = 1.0
@@ -611,7 +682,7 @@ class WhisperCB:
                       bias_list=bias_list, bias_boost=bias_boost, min_new_tokens=min_new_tokens,
                       prompt_ids=prompt_ids, return_dict_in_generate=return_dict_in_generate,
                       generation_config=generation_config, use_graph=use_graph, block=True,
-                      output_logprobs=output_logprobs)
+                      output_logprobs=output_logprobs, **rules_kw)
             if bias_lists is None and bias_list is None and bias_boost > 0 and bias_spans is not None:
                 kw["bias_list"], kw["bias_spans"] = self._spans_to_phrases(bias_spans), None
             if seeds is not None:
@@ -634,7 +705,10 @@ class WhisperCB:
                     return torch.cat(vals)
                 lp_w = max((p.token_logprobs.shape[1] for p in parts if p.token_logprobs is not None), default=0)
                 return GenerateOutput(sequences=out, token_logprobs=join("token_logprobs", lp_w),
-                                      avg_logprob=join("avg_logprob"), sequences_scores=join("sequences_scores"))
+                                      avg_logprob=join("avg_logprob"), sequences_scores=join("sequences_scores"),
+                                      segments=[s for p in parts for s in p.segments] if return_timestamps else None)
+            if return_timestamps:
+                return GenerateOutput(sequences=out, segments=[s for p in parts for s in p.segments])
             return GenerateOutput(sequences=out) if return_dict_in_generate else out
         gc = generation_config or self.generation_config
         max_length = int(max_length if max_length is not None else getattr(gc, "max_length", 448))
@@ -664,8 +738,12 @@ class WhisperCB:
         steps = C.c_int32(0)
         pre = np.asarray(prefix, dtype=np.int32)
         smp = _lib.WcbSampleCfg(T, seeds.ctypes.data_as(C.POINTER(C.c_uint64))) if seeds is not None else None
+        self._install_rules(rules)
         if output_logprobs:
-            return self._generate_scored(x, cfg, bl, bias_lists if bias_boost > 0 else None, prefix, pre, out, block, smp)
+            res = self._generate_scored(x, cfg, bl, bias_lists if bias_boost > 0 else None, prefix, pre, out, block, smp)
+            if return_timestamps:
+                res.segments = self._segments(res.sequences[:, len(prefix):].cpu().numpy())
+            return res
         if smp is not None:
             bb = BiasBatch(self, bias_lists) if (bias_lists is not None and bias_boost > 0) else None
             try:
@@ -696,7 +774,8 @@ class WhisperCB:
         ids = out[:, :steps.value].to(torch.int64)
         if return_dict_in_generate:
             sot = torch.tensor(prefix, dtype=torch.int64, device=self.device)[None].expand(B, -1)
-            return GenerateOutput(sequences=torch.cat([sot, ids], dim=1))
+            return GenerateOutput(sequences=torch.cat([sot, ids], dim=1),
+                                  segments=self._segments(ids.cpu().numpy()) if return_timestamps else None)
         return self._whisper_trim(ids)
 
     def _generate_scored(self, x, cfg, bl, bias_lists, prefix, pre, out, block, smp=None) -> GenerateOutput:
@@ -812,7 +891,9 @@ class WhisperCB:
 
     def decode_begin(self, encoder_outputs, prompt_ids=None, bias_list=None, bias_boost: float = 0.0,
                      min_new_tokens: int = 0, num_beams: int = 1, max_length: Optional[int] = None,
-                     bias_lists=None, logprobs: bool = False, temperature: float = 0.0, seed=0) -> "StepDecoder":
+                     bias_lists=None, logprobs: bool = False, temperature: float = 0.0, seed=0,
+                     return_timestamps: bool = False, suppress_tokens=None, begin_suppress_tokens=None,
+                     max_initial_timestamp: Optional[float] = None) -> "StepDecoder":
         """Step-wise decoding from an encoder output [B, 1500, d] (this model's dtype, on its device): the
         streaming form of generate() (wcb_decode_begin / wcb_decode_begin_beams). Greedy (num_beams = 1) or
         beam search (num_beams 2..8; `max_length` = generate()'s, the beams' length cap: None = the
@@ -822,7 +903,15 @@ class WhisperCB:
         `logprobs=True` (greedy): StepDecoder.logprobs() gives the token log-probs of the steps taken.
         `temperature > 0` (greedy): every step samples as generate(temperature=..., seed=...) does
         (wcb_decode_enable_sampling; `seed` an int through clip_seeds, or B per-clip seeds); step()'s scores are
-        then the winners' perturbed values."""
+        then the winners' perturbed values. `return_timestamps` / `suppress_tokens` / `begin_suppress_tokens` /
+        `max_initial_timestamp`: generate()'s token rules for every step of this decode (greedy only; timestamps
+        not with sampling: ValueError)."""
+        rules = self._rules_key_of(return_timestamps, suppress_tokens, begin_suppress_tokens, max_initial_timestamp)
+        if rules is not None:
+            if int(num_beams) != 1:
+                raise ValueError("suppress_tokens / begin_suppress_tokens / return_timestamps are greedy only: num_beams must be 1")
+            if return_timestamps and float(temperature) > 0.0:
+                raise ValueError("return_timestamps with sampling is not supported")
         enc = self._encoder_state(encoder_outputs)   # [B, 1500, d] checked: the library copies B·1500·d
         B = enc.shape[0]
         if B > 64:
@@ -858,6 +947,7 @@ class WhisperCB:
             bl = self.bias_list(bias_list) if (bias_list and bias_boost > 0) else None
         st = C.c_void_p()
         nb = int(num_beams)
+        self._install_rules(rules)
         if nb > 1 and max_length is not None:
             _lib.check(self._lib.wcb_decode_begin_beams(self._h, _ptr(enc), B, nb, pre.ctypes.data if pre is not None else None,
                                                         pre.shape[1] if pre is not None else 1, int(max_length),
