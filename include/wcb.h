@@ -84,6 +84,8 @@ const char* wcb_last_error(const wcb_handle* h);
  *   "decode_contexts" n  decode contexts in flight (1..4): calls decode on n streams from n buffers (4 is
  *                      refused while a step-wise decode owns context 3)
  *   "steps_per_graph" n  decode steps captured per replayed hipGraph (1..64, default 8)
+ *   "align_ws" n       MiB of the token-timestamp weights workspace (1..65536, default 1024): a batch above it is
+ *                      aligned in groups of clips (wcb_align); the frames do not depend on it
  *   "xenc_fm" 0/1      greedy encoder-space cross-attention reads the encoder output in the fragment-major chunk
  *                      layout (1, default; 1 KiB contiguous per load wave-instruction) or the row layout (0)
  *   "ring_kt" 1/2      decode rows > 64: 64-deep K sub-tiles per LDS-ring stage of the projection tiles
@@ -365,6 +367,60 @@ int wcb_token_rules_apply_host(const wcb_token_rules*, int vocab, int eos, const
 int wcb_op_lm_head_rules(int dtype, const void* A, const void* W, int M, int V, int K, int walkers,
                          const wcb_token_rules* rules, int eos, const int32_t* generated, int gen_ld,
                          const int32_t* lens, float* logits, long ld, int32_t* next_ids, void* stream);
+
+/* ---- token-level timestamps from cross-attention (HF return_token_timestamps / _extract_token_timestamps, per
+ * clip and batch-invariant; semantics: csrc/dtw.h). A teacher-forced post-pass over the ids any
+ * decode produced: the causal prefill of wcb_forward_enc with the LM head off and a capture kernel after the cross
+ * query of every layer that has selected heads; the column statistics, median filter, head mean, the DTW and its
+ * backtrace all run on the chip. For a clip with generated columns g[0..n), e = its first EOS (n: none), prefix
+ * length P, S_b = num_frames[b] / 2:
+ *   rows      i in [0, m), m = min(e, n - 1): the cross-attention of the position whose input is g[i] (P + i)
+ *   weights   softmax over all n_audio_ctx frames, cropped to S_b afterwards; per (head, frame) normalised over the
+ *             m rows (population std; a column with std 0 gives 0), median filter of `median_width` along the
+ *             frames (reflect padding), M = -(mean over the heads), f32
+ *   frame[i]  = the time index of the first DTW path cell of row i; rows >= m repeat frame[m - 1]; m <= 1: 0
+ * heads HOST [n_heads][2] = (layer, head) pairs (n_heads 0 / heads NULL: every head of the layers >= n_layers / 2);
+ * num_frames HOST [B] mel frames of every clip (NULL: all 2 * n_audio_ctx). */
+typedef struct { const int32_t* heads; int n_heads;
+                 int median_width;              /* odd, 1 .. 15 */
+                 const int32_t* num_frames; } wcb_align_cfg;
+/* ids int32 DEVICE [B][ld] (columns [0, n) read; ld >= n), prefix / prefix_len as wcb_generate, out_frames int32
+ * DEVICE [B][n], matrix_out f32 DEVICE [B][n - 1][n_audio_ctx] or NULL (rows < m, columns < S_b written).
+ * enc = encoder output [B][n_audio_ctx][d] in the model dtype (DEVICE, as wcb_forward_enc), or NULL: the encoder
+ * state the handle's latest wcb_generate* call left in its decode context — the pass is queued on that context's
+ * stream behind the decode (async_out decodes included), the next call's encoder waits for it, and `stream` is
+ * made to wait for the pass (no host wait); post-passes of one handle run one after the other, whichever decode
+ * context each uses: they share the handle's workspaces; WCB_ERR_STATE
+ * when there is none, B differs, or another call took the context since. WCB_ERR_ARG: a head out of range, more
+ * than 32 selected heads in one layer, an even or non-positive width, num_frames outside [2 * median_width,
+ * 2 * n_audio_ctx], B > 64, prefix_len + n - 1 > n_text_ctx; a width above 15: WCB_ERR_UNSUPPORTED. The weights
+ * workspace [clips][heads][n - 1][n_audio_ctx] f32 is bounded (1 GiB; option "align_ws", MiB): above it the clips are
+ * processed in groups, one teacher-forced pass per group. */
+int wcb_align(wcb_handle* h, const void* enc, int B, const int32_t* ids, int ld, int n, const int32_t* prefix,
+              int prefix_len, const wcb_align_cfg* cfg, int32_t* out_frames, float* matrix_out, void* stream);
+/* The capture kernel on caller operands, as one layer of one teacher-forced pass runs it: query rows q [clips * rps][ldq]
+ * in `dtype` (row clip * rps + j is position pos0 + j of that clip, head h at column h * q_hstride, `dim` values),
+ * keys by `layout`: 0 the cross-K cache [clips][H][S][64] (dim = 64), 1 the encoder output [clips][S][dim] in rows,
+ * 2 the same, laid out fragment-major by the op first (16-bit, the widths the encoder-space decode covers) ->
+ * w f32 DEVICE [nclip][nh][nrow][S]: for the clips [clip0, clip0 + nclip), the heads `heads` HOST [nh] and the
+ * alignment rows i = pos0 + j - P in [0, nrow), softmax over the S keys of q . key; other rows are not written.
+ * Blocks until done. */
+int wcb_op_align_capture(int dtype, const void* q, long ldq, int q_hstride, const void* keys, int layout, int clips,
+                         int H, int dim, int S, int rps, int pos0, int P, int nrow, int clip0, int nclip,
+                         const int32_t* heads, int nh, float* w, void* stream);
+/* The matrix kernel on caller operands: w f32 DEVICE [N][heads][m_max][S_ld], lens int32 DEVICE [N] (rows of every
+ * item), frames int32 DEVICE [N] (S_b of every item, NULL: S_ld) -> M f32 DEVICE [N][m_max][S_ld]. m_max <= 447. */
+int wcb_op_align_matrix(const float* w, int N, int heads, int m_max, int S_ld, const int32_t* lens,
+                        const int32_t* frames, int median_width, float* M, void* stream);
+/* The DTW kernel on caller operands: M f32 DEVICE [N][m_max][S_ld], lens / frames as above -> out_frames int32
+ * DEVICE [N][n_out] and, when path_text is non-NULL, the path as path_text / path_time int32 DEVICE [N][m_max +
+ * S_ld] with its length path_len int32 DEVICE [N]. Blocks until done (it may own a trace workspace). */
+int wcb_op_dtw(const float* M, int N, int m_max, int S_ld, const int32_t* lens, const int32_t* frames, int n_out,
+               int32_t* out_frames, int32_t* path_text, int32_t* path_time, int32_t* path_len, void* stream);
+/* HOST, no GPU: the same recurrence (csrc/dtw.h) on M [m][ld] (S columns read): frames [n_out] as above, and when
+ * path_text is non-NULL the path (capacity m + S each) and *path_len. */
+int wcb_dtw_host(const float* M, int m, int S, long ld, int32_t* frames, int n_out, int32_t* path_text,
+                 int32_t* path_time, int32_t* path_len);
 
 /* debug counters by name (not part of wcb_profile_read): "graph_captures" = decode graphs instantiated so
  * far on this handle. Unknown name: WCB_ERR_ARG. */

@@ -52,6 +52,22 @@ def token_rules(suppress=(), begin_suppress=(), timestamps=False, timestamp_begi
     return r, (sup, beg)
 
 
+class WcbAlignCfg(C.Structure):
+    _fields_ = [("heads", C.POINTER(C.c_int32)), ("n_heads", C.c_int), ("median_width", C.c_int),
+                ("num_frames", C.POINTER(C.c_int32))]
+
+
+def align_cfg(heads=None, median_width=7, num_frames=None):
+    """A WcbAlignCfg and the arrays it points into (keep both alive for the call)."""
+    import numpy as np
+    p32 = C.POINTER(C.c_int32)
+    hd = np.ascontiguousarray(np.asarray(heads, dtype=np.int32).reshape(-1, 2)) if heads is not None else None
+    nf = np.ascontiguousarray(np.asarray(num_frames, dtype=np.int32)) if num_frames is not None else None
+    cfg = WcbAlignCfg(hd.ctypes.data_as(p32) if hd is not None and len(hd) else None, len(hd) if hd is not None else 0,
+                      int(median_width), nf.ctypes.data_as(p32) if nf is not None else None)
+    return cfg, (hd, nf)
+
+
 class WcbTensorView(C.Structure):
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("dtype", C.c_int), ("ndim", C.c_int),
                 ("shape", C.c_int64 * 4), ("stride", C.c_int64 * 4)]
@@ -106,6 +122,12 @@ SIGNATURES = {
     "wcb_token_rules_apply_host": (C.c_int, [C.POINTER(WcbTokenRules), C.c_int, C.c_int, _P, C.c_int, _P]),
     "wcb_op_lm_head_rules": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(WcbTokenRules),
                                        C.c_int, _P, C.c_int, _P, _P, C.c_long, _P, _P]),
+    "wcb_align": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, _P, C.c_int, C.POINTER(WcbAlignCfg), _P, _P, _P]),
+    "wcb_op_align_capture": (C.c_int, [C.c_int, _P, C.c_long, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                       C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, _P]),
+    "wcb_op_align_matrix": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P]),
+    "wcb_op_dtw": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
+    "wcb_dtw_host": (C.c_int, [_P, C.c_int, C.c_int, C.c_long, _P, C.c_int, _P, _P, _P]),
     "wcb_debug_counter": (C.c_int, [_P, C.c_char_p, C.POINTER(C.c_int64)]),
     "wcb_debug_copy": (C.c_int, [_P, C.c_char_p, _P, C.c_int64, C.c_int]),
     "wcb_profile_enable": (C.c_int, [_P, C.c_int]),
@@ -142,6 +164,10 @@ class WcbArgError(WcbError, ValueError):
     """WCB_ERR_ARG: the reference raises ValueError for these (e.g. whisper_medical.py:87-90)."""
 
 
+class WcbStateError(WcbError):
+    """WCB_ERR_STATE: a call out of order (e.g. no encoder state held for wcb_align(enc = NULL))."""
+
+
 _lib = None
 
 
@@ -172,6 +198,6 @@ def check(rc: int, handle=None, what: str = ""):
     if rc < 0:
         lib = load()
         msg = lib.wcb_last_error(handle)
-        cls = WcbArgError if rc == -1 else WcbError
+        cls = WcbArgError if rc == -1 else WcbStateError if rc == -2 else WcbError
         raise cls(f"{what} failed ({rc}): {msg.decode() if msg else ''}")
     return rc

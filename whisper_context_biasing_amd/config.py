@@ -123,3 +123,24 @@ def parse_segments(ids, timestamp_begin, eos=None):
     if toks:
         segs.append((start, None, toks))
     return segs
+
+
+FRAME_SECONDS = 0.02        # one encoder position (two mel frames of 0.01 s)
+
+
+def words_from_token_times(ids, times, word_start, eos, audio_end=30.0):
+    """Words of one row of generated ids with a time per token (generate(return_token_timestamps=True)): a list of
+    (start_s, end_s, token_ids). A word starts at a text token whose `word_start` flag is set, or at the row's first
+    text token; ids >= `eos` (EOS, pads, special and timestamp tokens) are skipped; a word ends where the next one
+    starts, the last one at `audio_end` (the clip's num_frames * 0.01 s)."""
+    words = []
+    for t, sec in zip((int(v) for v in ids), times):
+        if t >= eos:
+            continue
+        if not words or word_start[t]:
+            words.append([float(sec), None, [t]])
+        else:
+            words[-1][2].append(t)
+    for i, w in enumerate(words):
+        w[1] = words[i + 1][0] if i + 1 < len(words) else float(audio_end)
+    return [(w[0], w[1], w[2]) for w in words]

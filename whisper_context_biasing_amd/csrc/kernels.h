@@ -390,6 +390,43 @@ inline bool lean_cfg(int K, int& nw, int& kpw) {
     default: return false;
   }
 }
+// ---- token-level timestamps (k_align.hip; semantics: dtw.h)
+constexpr int kAlignMaxRows = 447;        // rows of a clip's cost matrix: n_text_ctx - 1
+constexpr int kAlignMaxS = 1536;          // frames the capture kernel keeps in registers (Whisper: 1500)
+constexpr int kAlignMaxLayerHeads = 32;   // selected heads of one layer
+constexpr int kDtwLdsTrace = 128 * 1024;  // the DTW trace lives in LDS up to this size, in a workspace above it
+// ids [B][ld] → lens[b] = min(first EOS, n - 1); tf (nullable) [B][P + n - 1] = prefix (device; null: start_tok,
+// P = 1) then the first n - 1 generated ids
+void align_prep(const int* ids, int ld, int n, const int* prefix, int P, int start_tok, int eos, int vocab, int B,
+                int* tf, int* lens, hipStream_t s);
+// cross-attention weights of a layer's selected heads for the rows of one teacher-forced pass: activation row
+// clip·rps + j is position pos0 + j, alignment row i = pos0 + j - P (kept when 0 <= i < nrow), clips
+// [clip0, clip0 + nclip). xmode 0: q rows [·][ldq] (head h at h·64) against K [clips][H][S][64] of the layer;
+// xmode 1: q' rows (head h at h·dim) against the encoder output, row layout or xenc_to_fm's (fm).
+struct AlignCapArgs {
+  const void* q = nullptr; long ldq = 0; int q_hstride = 0;
+  const void* k = nullptr; long k_clip = 0;
+  int xmode = 0, fm = 0, dim = 64, S = 0;
+  int rps = 1, pos0 = 0, P = 1, nrow = 0, clip0 = 0, nclip = 0;
+  int nh = 0, heads_total = 0;
+  int head[kAlignMaxLayerHeads] = {}, slot[kAlignMaxLayerHeads] = {};   // head of the layer, its place in the list
+  float* w = nullptr;   // [nclip][heads_total][nrow][S]
+};
+void align_capture(DType t, const AlignCapArgs& a, hipStream_t s);
+// w [N][heads][m_max][S_ld], lens[N], frames[N] (S_b per item; null: S_ld) → M [N][m_max][S_ld] (rows < lens[b],
+// columns < S_b written); false: median width W not among 1, 3, .. 15
+bool align_matrix(const float* w, int N, int heads, int m_max, int S_ld, const int* lens, const int* frames, int W,
+                  float* M, hipStream_t s);
+struct DtwArgs {
+  const float* M = nullptr; int m_max = 0, S_ld = 0;   // [N][m_max][S_ld]
+  const int* lens = nullptr; const int* frames = nullptr;
+  int n_out = 0; int* out_frames = nullptr;            // [N][n_out]: rows >= m repeat the last row's frame
+  unsigned* trace = nullptr;                           // [N][m_max][words] when the trace does not fit in LDS
+  int* path_text = nullptr; int* path_time = nullptr; int* path_len = nullptr; int path_ld = 0;   // nullable
+};
+size_t dtw_trace_bytes(int m_max, int S_ld);
+void dtw(const DtwArgs& a, int N, hipStream_t s);
+
 void fill_i32(int* p, int v, long n, hipStream_t s);
 // dst[0..n) = host values, passed by value in the kernel arguments (stream-ordered, no host buffer
 // lifetime or pageable-copy ordering to worry about)

@@ -28,6 +28,7 @@
 #include "../../include/wcb.h"
 #include "kernels.h"
 #include "sample.h"
+#include "dtw.h"
 
 using namespace wcb;
 
@@ -390,6 +391,16 @@ struct wcb_handle {
   // per decode context: cross-K/V (xmode 0) or the encoder output (xmode 1); buffer k is read by
   // decode context k while the encoder stream fills the next one
   DevBuf xkv2[kMaxCtx];
+  // token timestamps (wcb_align): the post-pass's workspaces — w [clips of a group][heads][rows][S], the cost
+  // matrices, the teacher-forced ids, the per-clip rows and frames, the prefix, the DTW trace when it does not
+  // fit in LDS — and the decode context the latest wcb_generate* call left its encoder state in
+  DevBuf al_w, al_M, al_tf, al_lens, al_frames, al_prefix, al_trace;
+  int last_gen_buf = -1, last_gen_B = 0, last_gen_xm = 0, last_gen_id = -1;
+  // the workspaces are the handle's while a post-pass runs on its decode context's stream: every post-pass first
+  // waits for the one before it (ev_align), whichever context that ran in
+  hipEvent_t ev_align = nullptr;
+  bool align_pending = false;
+  size_t align_ws_bytes = (size_t)1 << 30;   // bound of al_w (option "align_ws", MiB): above it the clips go in groups
   // default (empty) bias automaton
   std::unique_ptr<wcb_bias> empty_bias;
   std::vector<wcb_bias*> biases;     // live automatons created on this handle (lifetime, wcb.h)
@@ -699,9 +710,10 @@ void wcb_destroy(wcb_handle* h) {
   for (auto& b : h->owned) b.release();
   for (DevBuf* b : {&h->dft, &h->dft3, &h->mel_lo, &h->mel_hi, &h->mel_w, &h->clip_max, &h->xt, &h->hbuf, &h->x, &h->h,
                     &h->qkv, &h->att, &h->ffn, &h->encout, &h->stamps, &h->stamp_acc, &h->dev_err, &h->rules_deny,
-                    &h->rules_deny0})
+                    &h->rules_deny0, &h->al_w, &h->al_M, &h->al_tf, &h->al_lens, &h->al_frames, &h->al_prefix, &h->al_trace})
     b->release();
   for (auto e : h->ev_pool) (void)hipEventDestroy(e);
+  if (h->ev_align) (void)hipEventDestroy(h->ev_align);
   if (h->ev_in) (void)hipEventDestroy(h->ev_in);
   if (h->ev_out) (void)hipEventDestroy(h->ev_out);
   if (h->he) (void)hipStreamDestroy(h->he);
@@ -727,7 +739,7 @@ int wcb_set_option(wcb_handle* h, const char* name, int value) {
     // writers published, the encoder-output layout): only the encoder-side and generate()-only options may
     // change under it (decode_contexts has its own check below).
     static const char* const kFreeWhileStepwise[] = {"decode_contexts", "enc_flash", "enc_gemm", "enc_raster",
-                                                     "steps_per_graph", "kq_cnt_seed"};
+                                                     "steps_per_graph", "kq_cnt_seed", "align_ws"};
     bool free_opt = false;
     for (const char* f : kFreeWhileStepwise) free_opt |= n == f;
     REQUIRE(free_opt || !h->step_state, "option " + n + ": a step-wise decode is active (wcb_decode_end first)");
@@ -772,6 +784,9 @@ int wcb_set_option(wcb_handle* h, const char* name, int value) {
         std::vector<unsigned long long> v(D.kq_cnt.bytes / 8, 4ull * (unsigned long long)value);
         HIPCHK(hipMemcpy(D.kq_cnt.p, v.data(), v.size() * 8, hipMemcpyHostToDevice));
       }
+    } else if (n == "align_ws") {
+      REQUIRE(value >= 1 && value <= 65536, "option align_ws: 1..65536 (MiB)");
+      h->align_ws_bytes = (size_t)value << 20;
     } else if (n == "steps_per_graph") {
       REQUIRE(value >= 1 && value <= 64, "option steps_per_graph: 1..64");
       h->steps_per_graph = value;
@@ -1357,6 +1372,18 @@ struct StepCfg {
   // head and the finalize, the timestamp grammar of the finalize (row state: two ints per row behind rowbase)
   const uint32_t* deny = nullptr; const uint32_t* deny0 = nullptr;
   TsRule ts;
+  // token timestamps: a teacher-forced pass (rps > 1, all rows in one chain) also captures the cross-attention
+  // weights of the selected heads. Null: the pass as it always was
+  const struct AlignPass* align = nullptr;
+};
+
+// the capture of one teacher-forced pass of wcb_align: per layer the selected (head, slot in the list) pairs; the
+// pass carries positions pos0 .. of every clip, alignment row i = position - P, clips [clip0, clip0 + nclip) kept
+struct AlignPass {
+  std::vector<std::vector<std::pair<int, int>>> by_layer;
+  int heads_total = 0, last_layer = 0;
+  int P = 1, nrow = 0, pos0 = 0, clip0 = 0, nclip = 0;
+  float* w = nullptr;   // [nclip][heads_total][nrow][S]
 };
 
 // the handle's token rules into a greedy step configuration
@@ -1382,6 +1409,34 @@ bool xfm_possible(const wcb_handle* h) {
 // the folded LayerNorm of the > 64-row projections is available (16-bit, d a multiple of 32)
 bool lnf_possible(const wcb_handle* h) {
   return h->ln_fold && h->dt != kF32 && h->d.d_model % 32 == 0 && h->d.d_model <= kLnfMaxK;
+}
+
+// wcb_align's capture after the cross query of layer l: q = the layer's cross query rows (xmode 0: q [M][d]) or
+// their encoder-space form (xmode 1: q' [M][H·d]); the keys are the context's cross-K of the layer or its encoder
+// output, whichever layout the decode reads
+void align_hook(wcb_handle* h, const StepCfg& c, int l, const void* q, int rps, hipStream_t st_) {
+  const AlignPass& ap = *c.align;
+  const auto& hl = ap.by_layer[l];
+  if (hl.empty()) return;
+  const int d = h->d.d_model, S = h->S(), H = h->H(), clips = c.clips ? c.clips : c.B;
+  const size_t e = esize(h->d.dtype);
+  AlignCapArgs a;
+  a.q = q; a.xmode = c.xmode; a.S = S;
+  if (c.xmode == 1) {
+    a.ldq = (long)H * d; a.q_hstride = d; a.dim = d;
+    a.k = h->xkv2[c.buf].p; a.fm = xenc_fm_on(h);
+    a.k_clip = a.fm ? xenc_fm_elems(1, S, d) : (long)S * d;
+  } else {
+    a.ldq = d; a.q_hstride = 64; a.dim = 64;
+    a.k = (const char*)h->xkv2[c.buf].p + (size_t)l * 2 * clips * H * S * 64 * e;
+    a.k_clip = (long)H * S * 64;
+  }
+  a.rps = rps; a.pos0 = ap.pos0; a.P = ap.P; a.nrow = ap.nrow; a.clip0 = ap.clip0; a.nclip = ap.nclip;
+  a.nh = (int)hl.size(); a.heads_total = ap.heads_total;
+  for (int i = 0; i < a.nh; ++i) { a.head[i] = hl[i].first; a.slot[i] = hl[i].second; }
+  a.w = ap.w;
+  h->timed("align_capture", 2.0 * ap.nclip * rps * a.nh * (double)S * a.dim,
+           (double)ap.nclip * rps * a.nh * S * 4.0, st_, [&] { align_capture(h->dt, a, st_); });
 }
 
 // Decoder layers + LM head for rows [b0, b0 + nb) of the batch on stream `st_`: WhisperDecoder.forward
@@ -1528,6 +1583,10 @@ void decode_rows(wcb_handle* h, const StepCfg& c, int b0, int nb, int chain, hip
         kq.a_grp_n = d; kq.a_grp_off = 64; kq.W_fm = w.xkt_fm;
         proj("dec_kq", kq);
       }
+      if (c.align) {
+        align_hook(h, c, l, dqp, rps, st_);
+        if (l == c.align->last_layer) break;   // nothing past the last selected layer's query is read
+      }
       XencArgs xa;
       xa.fm = xenc_fm_on(h);
       xa.enc = h->xkv2[c.buf].p; xa.enc_sb = xa.fm ? xenc_fm_elems(1, S, d) : (long)S * d;
@@ -1565,6 +1624,10 @@ void decode_rows(wcb_handle* h, const StepCfg& c, int b0, int nb, int chain, hip
       xq.bias = w.xq_b; xq.ln_u = w.lnx_u; xq.ln_c = w.lnx_c; xq.ln_wg = w.xq_wg; xq.W_fm = w.xq_fm; xq.ln_wg_fm = w.xq_wgfm;
       if (x16fm) { xq.ln_a16 = x16fm; xq.a_fm = 1; }
       proj("dec_xq", xq);
+      if (c.align) {
+        align_hook(h, c, l, dq, rps, st_);
+        if (l == c.align->last_layer) break;
+      }
       AttnArgs xa;
       const char* xkv = (const char*)h->xkv2[c.buf].p + l * xkv_l * e;
       xa.q = dq; xa.ldq = d; xa.q_Sb = 1; xa.Sq = 1;
@@ -1991,6 +2054,7 @@ static void generate_impl(wcb_handle* h, const float* mel, int B, const wcb_gen_
     const int xm = nb > 1 ? h->beam_xmode : h->xmode;   // this call's cross-attention formulation
     ensure_dec_ws(h, B, R, Tc, out_ld, xm, P > 1 ? R * std::min(prefill_chunk(R), P - 1) : R);
     const int buf = h->gen_count++ % h->nctx;
+    h->last_gen_buf = buf; h->last_gen_B = B; h->last_gen_xm = xm; h->last_gen_id = h->gen_count;   // (wcb_align, enc = NULL)
     DecCtx& D = h->dc[buf];
     // beam state [R] / [R][max_new] / [R][Tc] / [R][K] / [B][2] in one buffer
     if (nb > 1) ensure_beam_buf(h, D, B, nb, cfg->max_new_tokens, Tc);
@@ -2610,6 +2674,239 @@ int wcb_forward_enc(wcb_handle* h, const void* enc, int B, const int32_t* dec_id
     HIPCHK(hipEventRecord(h->ev_xkv[buf], h->he));
     forward_decode(h, buf, B, dec_ids, T, logits);
     sync_out(h, stream, h->dc[buf].hs);
+  });
+}
+
+// ---- token-level timestamps (wcb.h)
+static void check_median_width(int W) {
+  REQUIRE(W >= 1 && (W & 1), "median_width must be odd and positive");
+  if (W > 15) throw WcbError(WCB_ERR_UNSUPPORTED, "median_width above 15 is not supported");
+}
+
+int wcb_align(wcb_handle* h, const void* enc, int B, const int32_t* ids, int ld, int n, const int32_t* prefix,
+              int prefix_len, const wcb_align_cfg* cfg, int32_t* out_frames, float* matrix_out, void* stream) {
+  return guarded(h, [&] {
+    REQUIRE(h && ids && cfg && out_frames && B > 0 && n > 0 && ld >= n, "bad argument");
+    if (!h->ready) throw WcbError(WCB_ERR_STATE, "weights not finalized");
+    REQUIRE(B <= 64, "batch > 64 per handle: split the batch");
+    const int P = prefix ? prefix_len : 1;
+    REQUIRE(P >= 1, "prefix_len must be >= 1");
+    const int T = P + n - 1, nrow = n - 1, S = h->S(), L = h->d.n_layers, H = h->H();
+    REQUIRE(T <= h->d.n_text_ctx, "prefix + generated ids exceed max_target_positions");
+    check_median_width(cfg->median_width);
+    if (S > kAlignMaxS) throw WcbError(WCB_ERR_UNSUPPORTED, "token timestamps: more than 1536 encoder positions");
+    AlignPass ap;
+    ap.by_layer.resize(L);
+    if (cfg->heads && cfg->n_heads > 0) {
+      for (int i = 0; i < cfg->n_heads; ++i) {
+        const int l = cfg->heads[2 * i], hd = cfg->heads[2 * i + 1];
+        REQUIRE(l >= 0 && l < L && hd >= 0 && hd < H, "alignment head (" + std::to_string(l) + ", " + std::to_string(hd) +
+                                                          ") outside the model's layers / heads");
+        ap.by_layer[l].push_back({hd, i});
+      }
+      ap.heads_total = cfg->n_heads;
+    } else {   // OpenAI's default when a checkpoint names none: every head of the upper half of the layers
+      for (int l = L / 2; l < L; ++l)
+        for (int hd = 0; hd < H; ++hd) ap.by_layer[l].push_back({hd, ap.heads_total++});
+    }
+    for (int l = 0; l < L; ++l) {
+      REQUIRE((int)ap.by_layer[l].size() <= kAlignMaxLayerHeads, "more than 32 alignment heads in one layer");
+      if (!ap.by_layer[l].empty()) ap.last_layer = l;
+    }
+    std::vector<int> sb(B, S);
+    if (cfg->num_frames)
+      for (int b = 0; b < B; ++b) {
+        REQUIRE(cfg->num_frames[b] >= 2 * cfg->median_width && cfg->num_frames[b] <= 2 * S,
+                "num_frames outside [2 * median_width, 2 * n_audio_ctx]");
+        sb[b] = cfg->num_frames[b] / 2;
+      }
+    int buf, xm;
+    const int rows = B * std::min(prefill_chunk(B), T);
+    if (enc) {
+      xm = h->xmode;
+      ensure_dec_ws(h, B, B, T, 1, xm, rows);
+      buf = h->gen_count++ % h->nctx;
+    } else {
+      if (h->last_gen_buf < 0 || h->last_gen_id != h->gen_count)
+        throw WcbError(WCB_ERR_STATE, "wcb_align(enc = NULL): no encoder state of a wcb_generate call is held");
+      if (h->last_gen_B != B)
+        throw WcbError(WCB_ERR_STATE, "wcb_align(enc = NULL): the latest wcb_generate call had " +
+                                          std::to_string(h->last_gen_B) + " clips, this call has " + std::to_string(B));
+      buf = h->last_gen_buf;
+      xm = h->last_gen_xm;
+      ensure_dec_ws(h, B, B, T, 1, xm, rows);   // (the encoder-side buffer already has its size: kept)
+    }
+    DecCtx& D = h->dc[buf];
+    // workspaces (a reallocation drains the streams first: an earlier post-pass may still read them)
+    const size_t per_clip = (size_t)ap.heads_total * std::max(nrow, 1) * S * 4;
+    const int gsz = (int)std::min<size_t>(B, std::max<size_t>(1, h->align_ws_bytes / per_clip));
+    const size_t trace_clip = dtw_trace_bytes(nrow, S);
+    const bool trace_ws = trace_clip > (size_t)kDtwLdsTrace;
+    const size_t need[] = {gsz * per_clip, matrix_out ? 0 : (size_t)B * std::max(nrow, 1) * S * 4, (size_t)B * T * 4,
+                           (size_t)B * 4, (size_t)B * 4, (size_t)P * 4, trace_ws ? B * trace_clip : 0};
+    DevBuf* have[] = {&h->al_w, &h->al_M, &h->al_tf, &h->al_lens, &h->al_frames, &h->al_prefix, &h->al_trace};
+    bool grow = false;
+    for (int i = 0; i < 7; ++i) grow |= need[i] > have[i]->bytes;
+    if (grow) {
+      quiesce(h);
+      for (int i = 0; i < 7; ++i) have[i]->ensure(need[i]);
+    }
+    if (enc) {   // the given encoder output into the context, as wcb_forward_enc
+      sync_in(h, stream, h->he);
+      HIPCHK(hipStreamWaitEvent(h->he, h->ev_dec[buf], 0));
+      if (xm == 1) fill_xenc(h, buf, enc, B, h->he);
+      else cross_kv(h, B, buf, enc);
+      HIPCHK(hipEventRecord(h->ev_xkv[buf], h->he));
+      HIPCHK(hipStreamWaitEvent(D.hs, h->ev_xkv[buf], 0));
+    }
+    sync_in(h, stream, D.hs);   // the ids
+    if (h->align_pending) HIPCHK(hipStreamWaitEvent(D.hs, h->ev_align, 0));   // the workspaces: one pass at a time
+    int* tf = h->al_tf.as<int>();
+    int* lens = h->al_lens.as<int>();
+    int* frames = h->al_frames.as<int>();
+    float* M = matrix_out ? matrix_out : h->al_M.as<float>();
+    if (prefix) write_i32(h->al_prefix.as<int>(), prefix, P, D.hs);
+    write_i32(frames, sb.data(), B, D.hs);
+    align_prep(ids, ld, n, prefix ? h->al_prefix.as<int>() : nullptr, P, h->d.decoder_start_token_id, h->d.eos_token_id,
+               h->d.vocab, B, tf, lens, D.hs);
+    ap.P = P; ap.nrow = nrow; ap.w = h->al_w.as<float>();
+    int* ints = D.ints.as<int>();
+    for (int c0 = 0; c0 < B && nrow > 0; c0 += gsz) {
+      ap.clip0 = c0; ap.nclip = std::min(gsz, B - c0);
+      // teacher forcing over prefix + ids, LM head off: the causal prefill of wcb_forward_enc
+      HIPCHK(hipMemsetAsync(ints, 0, (size_t)(I_NEXT + 4 * B) * 4, D.hs));
+      for (int p0 = 0, np; p0 < T; p0 += np) {
+        np = std::min(prefill_chunk(B), T - p0);
+        StepCfg sc{B, T, 1, buf, false, false, nullptr, 0, nullptr, 0.f, 0, nullptr, 0};
+        sc.xmode = xm;
+        ap.pos0 = p0;
+        sc.align = p0 + np > P ? &ap : nullptr;   // (a pass over prefix positions alone has no row to keep)
+        prefill_step(h, sc, np, tf, T);
+      }
+      h->timed("align_matrix", 0, (double)ap.nclip * per_clip, D.hs, [&] {
+        if (!align_matrix(ap.w, ap.nclip, ap.heads_total, nrow, S, lens + c0, frames + c0, cfg->median_width,
+                          M + (size_t)c0 * nrow * S, D.hs))
+          throw WcbError(WCB_ERR_UNSUPPORTED, "median_width not supported");
+      });
+    }
+    DtwArgs da;
+    da.M = M; da.m_max = nrow; da.S_ld = S; da.lens = lens; da.frames = frames; da.n_out = n; da.out_frames = out_frames;
+    da.trace = trace_ws ? h->al_trace.as<unsigned>() : nullptr;
+    h->timed("align_dtw", 0, (double)B * nrow * S * 4, D.hs, [&] { dtw(da, B, D.hs); });
+    HIPCHK(hipEventRecord(h->ev_dec[buf], D.hs));
+    if (!h->ev_align) HIPCHK(hipEventCreateWithFlags(&h->ev_align, hipEventDisableTiming));
+    HIPCHK(hipEventRecord(h->ev_align, D.hs));
+    h->align_pending = true;
+    sync_out(h, stream, D.hs);
+  });
+}
+
+int wcb_op_align_capture(int dtype, const void* q, long ldq, int q_hstride, const void* keys, int layout, int clips,
+                         int H, int dim, int S, int rps, int pos0, int P, int nrow, int clip0, int nclip,
+                         const int32_t* heads, int nh, float* w, void* stream) {
+  return guarded(nullptr, [&] {
+    REQUIRE(q && keys && heads && w && clips > 0 && H > 0 && rps > 0 && nrow > 0 && P >= 1 && pos0 >= 0, "bad argument");
+    REQUIRE(dtype >= 0 && dtype <= 2 && layout >= 0 && layout <= 2, "dtype 0..2, layout 0..2");
+    REQUIRE(clip0 >= 0 && nclip > 0 && clip0 + nclip <= clips, "clip range outside the batch");
+    REQUIRE(nh >= 1 && nh <= kAlignMaxLayerHeads, "1..32 heads");
+    REQUIRE(S >= 1 && S <= kAlignMaxS, "S must be in [1, 1536]");
+    REQUIRE(layout == 0 ? dim == 64 : dim % 32 == 0 && dim >= 32, "dim: 64 against the K cache, a multiple of 32 otherwise");
+    REQUIRE(q_hstride >= dim && ldq >= (long)q_hstride, "q strides");
+    if (layout == 2 && !xenc_supported((DType)dtype, dim))
+      throw WcbError(WCB_ERR_UNSUPPORTED, "no fragment-major encoder layout for this dtype / width");
+    hipStream_t st = (hipStream_t)stream;
+    AlignCapArgs a;
+    a.q = q; a.ldq = ldq; a.q_hstride = q_hstride; a.k = keys; a.xmode = layout != 0; a.dim = dim; a.S = S;
+    a.k_clip = layout == 0 ? (long)H * S * 64 : (long)S * dim;
+    DevBuf fm;
+    if (layout == 2) {
+      fm.ensure((size_t)xenc_fm_elems(clips, S, dim) * 2);
+      xenc_to_fm((DType)dtype, keys, fm.p, clips, S, dim, st);
+      a.k = fm.p; a.fm = 1; a.k_clip = xenc_fm_elems(1, S, dim);
+    }
+    a.rps = rps; a.pos0 = pos0; a.P = P; a.nrow = nrow; a.clip0 = clip0; a.nclip = nclip; a.nh = nh; a.heads_total = nh;
+    for (int i = 0; i < nh; ++i) {
+      REQUIRE(heads[i] >= 0 && heads[i] < H, "head outside [0, H)");
+      a.head[i] = heads[i]; a.slot[i] = i;
+    }
+    a.w = w;
+    align_capture((DType)dtype, a, st);
+    const hipError_t e = hipStreamSynchronize(st);
+    fm.release();
+    HIPCHK(e);
+    HIPCHK(hipGetLastError());
+  });
+}
+
+int wcb_op_align_matrix(const float* w, int N, int heads, int m_max, int S_ld, const int32_t* lens, const int32_t* frames,
+                        int median_width, float* M, void* stream) {
+  return guarded(nullptr, [&] {
+    REQUIRE(w && lens && M && N > 0 && heads > 0 && S_ld > 0, "bad argument");
+    REQUIRE(m_max >= 1 && m_max <= kAlignMaxRows, "m_max must be in [1, 447]");
+    check_median_width(median_width);
+    if (!align_matrix(w, N, heads, m_max, S_ld, lens, frames, median_width, M, (hipStream_t)stream))
+      throw WcbError(WCB_ERR_UNSUPPORTED, "median_width not supported");
+    HIPCHK(hipGetLastError());
+  });
+}
+
+int wcb_op_dtw(const float* M, int N, int m_max, int S_ld, const int32_t* lens, const int32_t* frames, int n_out,
+               int32_t* out_frames, int32_t* path_text, int32_t* path_time, int32_t* path_len, void* stream) {
+  return guarded(nullptr, [&] {
+    REQUIRE(M && lens && out_frames && N > 0 && S_ld > 0 && n_out >= m_max, "bad argument (n_out >= m_max)");
+    REQUIRE(m_max >= 1 && m_max <= kAlignMaxRows, "m_max must be in [1, 447]");
+    REQUIRE(!path_text == !path_time && (!path_text || path_len), "path_text, path_time and path_len go together");
+    DevBuf trace;
+    const size_t tb = dtw_trace_bytes(m_max, S_ld);
+    if (tb > (size_t)kDtwLdsTrace) trace.ensure((size_t)N * tb);
+    DtwArgs a;
+    a.M = M; a.m_max = m_max; a.S_ld = S_ld; a.lens = lens; a.frames = frames; a.n_out = n_out; a.out_frames = out_frames;
+    a.trace = trace.as<unsigned>();
+    a.path_text = path_text; a.path_time = path_time; a.path_len = path_len; a.path_ld = m_max + S_ld;
+    hipError_t e = hipSuccess;
+    dtw(a, N, (hipStream_t)stream);
+    e = hipStreamSynchronize((hipStream_t)stream);
+    trace.release();
+    HIPCHK(e);
+    HIPCHK(hipGetLastError());
+  });
+}
+
+int wcb_dtw_host(const float* M, int m, int S, long ld, int32_t* frames, int n_out, int32_t* path_text, int32_t* path_time,
+                 int32_t* path_len) {
+  return guarded(nullptr, [&] {
+    REQUIRE(M && frames && m >= 0 && S >= 1 && ld >= S && n_out > 0, "bad argument");
+    REQUIRE(!path_text == !path_time && (!path_text || path_len), "path_text, path_time and path_len go together");
+    for (int i = 0; i < n_out; ++i) frames[i] = 0;
+    if (path_len) *path_len = 0;
+    if (m == 0) return;
+    // two cost columns' worth of state would do; the rows are kept whole for clarity: prev = cost[i-1][·]
+    std::vector<float> prev((size_t)S + 1, INFINITY), cur((size_t)S + 1);
+    std::vector<uint8_t> trace((size_t)m * S);
+    prev[0] = 0.f;
+    for (int i = 1; i <= m; ++i) {
+      cur[0] = INFINITY;
+      for (int j = 1; j <= S; ++j)
+        trace[(size_t)(i - 1) * S + j - 1] =
+            (uint8_t)dtw_cell(prev[j - 1], prev[j], cur[j - 1], M[(size_t)(i - 1) * ld + j - 1], cur[j]);
+      std::swap(prev, cur);
+    }
+    int i = m, j = S, len = 0, last = 0;
+    while (i > 0 || j > 0) {
+      if (path_text) { path_text[len] = i - 1; path_time[len] = j - 1; }
+      ++len;
+      if (i >= 1 && i - 1 < n_out) frames[i - 1] = j - 1;
+      if (i == m) last = j - 1;
+      const int stored = (i > 0 && j > 0) ? trace[(size_t)(i - 1) * S + j - 1] : 0;
+      dtw_back(dtw_border(i, j, stored), i, j);
+    }
+    if (m <= 1) last = 0;
+    for (int r = m; r < n_out; ++r) frames[r] = last;
+    if (path_text) {
+      std::reverse(path_text, path_text + len);
+      std::reverse(path_time, path_time + len);
+    }
+    if (path_len) *path_len = len;
   });
 }
 

@@ -31,7 +31,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .config import N_SAMPLES, TIME_PRECISION, WhisperDims, dims_from_hf_config, get_dims, parse_segments, timestamp_ids
+from .config import (FRAME_SECONDS, N_SAMPLES, TIME_PRECISION, WhisperDims, dims_from_hf_config, get_dims, parse_segments,
+                     timestamp_ids, words_from_token_times)
 
 _TORCH_DT = {_lib.WCB_BF16: torch.bfloat16, _lib.WCB_F16: torch.float16, _lib.WCB_F32: torch.float32}
 
@@ -97,6 +98,11 @@ class GenerateOutput:
     # generate(return_timestamps=True): per clip a list of (start_s, end_s, token_ids) parsed on the host from the
     # generated ids (config.parse_segments); end_s None for a trailing segment without a closing timestamp
     segments: Optional[list] = None
+    # generate(return_token_timestamps=True): token_timestamps [B, P + n] f32 seconds, aligned with `sequences` (0 over
+    # the prefix, as HF), from the DTW over the cross-attention of a teacher-forced pass (wcb_align); `words`, when
+    # the model has a word_start mask: per clip a list of (start_s, end_s, token_ids) (config.words_from_token_times)
+    token_timestamps: Optional[torch.Tensor] = None
+    words: Optional[list] = None
 
 
 @dataclass
@@ -572,7 +578,8 @@ class WhisperCB:
                  do_sample: Optional[bool] = None, logprob_threshold: Optional[float] = -1.0,
                  compression_ratio_threshold: Optional[float] = 2.4, return_timestamps: bool = False,
                  suppress_tokens=None, begin_suppress_tokens=None, max_initial_timestamp: Optional[float] = None,
-                 **kwargs):
+                 return_token_timestamps: bool = False, alignment_heads=None, num_frames=None,
+                 median_filter_width: int = 7, **kwargs):
         """Greedy (num_beams = 1, the reference's eval setting) or HF beam
         search (num_beams = 2..8, [tf] generation/utils.py:3208) on the device.
 
@@ -623,9 +630,36 @@ class WhisperCB:
         and returns a GenerateOutput whose `segments` holds per clip a list of (start_s, end_s, token_ids);
         `max_initial_timestamp=1.0` (seconds) bounds the first timestamp. Greedy only: with `num_beams > 1`, and
         for timestamps also with `temperature > 0` or a temperature sequence, the call raises ValueError.
+
+        `return_token_timestamps=True` (HF's; implies `return_dict_in_generate`, needs `block=True`) adds
+        `token_timestamps` [B, P + n] f32 seconds — when each token was spoken — from a teacher-forced post-pass over
+        the ids the decode produced (wcb_align: cross-attention of `alignment_heads`, a list of (layer, head), default
+        every head of the upper half of the layers; normalised, median-filtered over `median_filter_width` frames, DTW
+        on the device). It works with every decode mode above and changes none of them. `num_frames` = mel frames of
+        every clip ([B] ints, default 3000) crops the alignment to each clip's audio. With a `word_start` mask set the
+        result also holds `words`.
         """
         if not self._loaded:
             raise _lib.WcbError("weights not loaded")
+        if return_token_timestamps:
+            if not block:
+                raise ValueError("return_token_timestamps reads the ids of the finished decode: block=False is not supported")
+            input_features = self._features(input_features)
+            B_all = int(input_features.shape[0])
+            akw = self._align_args(B_all, alignment_heads, num_frames, median_filter_width)   # ValueError before any work
+            res = self.generate(input_features, labels=labels, bias_spans=bias_spans, max_length=max_length,
+                                num_beams=num_beams, bias_list=bias_list, bias_boost=bias_boost,
+                                min_new_tokens=min_new_tokens, prompt_ids=prompt_ids, return_dict_in_generate=True,
+                                generation_config=generation_config, use_graph=use_graph, block=True,
+                                bias_lists=bias_lists, per_utterance_bias=per_utterance_bias,
+                                output_logprobs=output_logprobs, temperature=temperature, seed=seed, do_sample=do_sample,
+                                logprob_threshold=logprob_threshold,
+                                compression_ratio_threshold=compression_ratio_threshold,
+                                return_timestamps=return_timestamps, suppress_tokens=suppress_tokens,
+                                begin_suppress_tokens=begin_suppress_tokens,
+                                max_initial_timestamp=max_initial_timestamp, **kwargs)
+            P = 1 + (len(prompt_ids) if prompt_ids is not None else 0)
+            return self._attach_token_timestamps(res, input_features, P, akw)
         if output_logprobs or return_timestamps:
             return_dict_in_generate = True
         rules_kw = dict(return_timestamps=return_timestamps, suppress_tokens=suppress_tokens,
@@ -997,6 +1031,121 @@ class WhisperCB:
             if n < W:
                 out[i, n:] = pad
         return out
+
+    # ------------------------------------------------------------------------- token timestamps
+    def _align_args(self, B: int, alignment_heads, num_frames, median_filter_width) -> dict:
+        """The checked alignment arguments (ValueError for what wcb_align refuses)."""
+        W = int(median_filter_width)
+        if W < 1 or W % 2 == 0:
+            raise ValueError(f"median_filter_width must be odd and positive, got {median_filter_width!r}")
+        if W > 15:
+            raise ValueError("median_filter_width above 15 is not supported")
+        heads = None
+        if alignment_heads is not None:
+            heads = [(int(l), int(h)) for l, h in alignment_heads]
+            if not heads:
+                raise ValueError("alignment_heads is empty")
+            for l, h in heads:
+                if not (0 <= l < self.dims.n_layers and 0 <= h < self.dims.n_heads):
+                    raise ValueError(f"alignment head ({l}, {h}) outside {self.dims.n_layers} layers x {self.dims.n_heads} heads")
+            for l in {l for l, _ in heads}:
+                if sum(1 for x, _ in heads if x == l) > 32:
+                    raise ValueError("more than 32 alignment heads in one layer")
+        nf = None
+        if num_frames is not None:
+            nf = np.asarray(num_frames, dtype=np.int64).reshape(-1)
+            if nf.shape[0] == 1 and B > 1:
+                nf = np.repeat(nf, B)
+            if nf.shape[0] != B:
+                raise ValueError(f"num_frames has {nf.shape[0]} entries, the batch {B} clips")
+            if (nf < 2 * W).any() or (nf > 2 * self.dims.n_audio_ctx).any():
+                raise ValueError(f"num_frames must lie in [{2 * W}, {2 * self.dims.n_audio_ctx}]")
+        return dict(heads=heads, num_frames=nf, width=W)
+
+    def _align_call(self, enc, ids: torch.Tensor, prefix, akw, nf, matrix: bool = False):
+        """wcb_align on one batch of at most 64 clips: ids int32 [B, n] (device) -> frames int32 [B, n] (and the cost
+        matrices [B, n - 1, n_audio_ctx] f32 when `matrix`)."""
+        B, n = ids.shape
+        frames = torch.empty(B, n, dtype=torch.int32, device=self.device)
+        mat = torch.zeros(B, max(n - 1, 1), self.dims.n_audio_ctx, dtype=torch.float32, device=self.device) if matrix else None
+        cfg, keep = _lib.align_cfg(akw["heads"], akw["width"], nf)
+        pre = np.asarray(prefix, dtype=np.int32)
+        _lib.check(self._lib.wcb_align(self._h, _ptr(enc) if enc is not None else None, B, _ptr(ids), ids.stride(0), n,
+                                       pre.ctypes.data if len(prefix) > 1 else None, len(prefix), C.byref(cfg),
+                                       _ptr(frames), _ptr(mat) if mat is not None else None, _stream(self.device)),
+                   self._h, "wcb_align")
+        del keep
+        return (frames, mat) if matrix else frames
+
+    def _attach_token_timestamps(self, res: GenerateOutput, input_features, P: int, akw) -> GenerateOutput:
+        """token_timestamps (and words) of a finished generate(): through the encoder state the decode left in its
+        context when the library still holds it for exactly this batch (one library call decoded it: the library's own
+        check, WCB_ERR_STATE otherwise), else re-encoded in batches of at most 64 clips."""
+        seq = res.sequences
+        B = seq.shape[0]
+        prefix = [int(t) for t in seq[0, :P].tolist()]
+        ids = seq[:, P:].to(torch.int32).contiguous()
+        nf = akw["num_frames"]
+        frames = None
+        if ids.shape[1] == 0:
+            frames = torch.zeros(B, 0, dtype=torch.int32, device=self.device)
+        elif B <= 64:
+            try:
+                frames = self._align_call(None, ids, prefix, akw, nf)
+            except _lib.WcbStateError:
+                frames = None
+        if frames is None:
+            x = self._features(input_features)
+            parts = []
+            for i in range(0, B, 64):
+                enc = self.encode(x[i:i + 64])
+                parts.append(self._align_call(enc, ids[i:i + 64].contiguous(), prefix, akw, nf[i:i + 64] if nf is not None else None))
+            frames = torch.cat(parts)
+        ts = torch.zeros(B, seq.shape[1], dtype=torch.float32, device=self.device)
+        ts[:, P:] = frames.to(torch.float32) * FRAME_SECONDS
+        res.token_timestamps = ts
+        if self._word_start is not None:
+            ids_h, t_h = ids.cpu().numpy(), ts[:, P:].cpu().numpy()
+            res.words = [words_from_token_times(ids_h[b], t_h[b], self._word_start, self.dims.eos_token_id,
+                                                (float(nf[b]) if nf is not None else 2.0 * self.dims.n_audio_ctx) * 0.01)
+                         for b in range(B)]
+        return res
+
+    def align(self, encoder_outputs, sequences, prefix_len: int = 1, alignment_heads=None, num_frames=None,
+              median_filter_width: int = 7, return_matrix: bool = False):
+        """Forced alignment of given token sequences: `sequences` [B, P + n] (the first `prefix_len` = P columns the
+        shared prompt ending in decoder_start, as generate()'s `.sequences`) against `encoder_outputs` [B, 1500, d]
+        -> token_timestamps [B, P + n] f32 seconds (0 over the prefix), exactly what
+        generate(return_token_timestamps=True) returns for those sequences. `return_matrix` also returns the DTW's
+        cost matrices [B, n - 1, 1500] f32 (rows below each clip's length and columns below its frames are
+        meaningful)."""
+        if not self._loaded:
+            raise _lib.WcbError("weights not loaded")
+        seq = torch.as_tensor(sequences).to(self.device)
+        if seq.dim() != 2:
+            raise ValueError("sequences must be [B, P + n]")
+        B, P = seq.shape[0], int(prefix_len)
+        if not 1 <= P < seq.shape[1]:
+            raise ValueError(f"prefix_len must lie in [1, {seq.shape[1] - 1}]")
+        if P + (seq.shape[1] - P) - 1 > self.dims.n_text_ctx:
+            raise ValueError("sequences longer than max_target_positions")
+        if B > 64:
+            raise ValueError("align takes at most 64 clips per call")
+        if bool(((seq < 0) | (seq >= self.dims.vocab)).any()):
+            raise ValueError(f"token ids outside [0, {self.dims.vocab})")
+        if bool((seq[:, :P] != seq[:1, :P]).any()):
+            raise ValueError("the prefix columns must be the same for every clip")
+        akw = self._align_args(B, alignment_heads, num_frames, median_filter_width)
+        enc = self._encoder_state(encoder_outputs)
+        if enc.shape[0] != B:
+            raise ValueError(f"encoder_outputs has {enc.shape[0]} clips, sequences {B}")
+        prefix = [int(t) for t in seq[0, :P].tolist()]
+        ids = seq[:, P:].to(torch.int32).contiguous()
+        out = self._align_call(enc, ids, prefix, akw, akw["num_frames"], matrix=return_matrix)
+        frames, mat = out if return_matrix else (out, None)
+        ts = torch.zeros(B, seq.shape[1], dtype=torch.float32, device=self.device)
+        ts[:, P:] = frames.to(torch.float32) * FRAME_SECONDS
+        return (ts, mat) if return_matrix else ts
 
     kRetiredMax = 32
 
