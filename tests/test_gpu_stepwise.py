@@ -251,3 +251,39 @@ def test_decode_contexts_guard_while_stepwise_decode_is_open():
     dec.close()
     assert np.array_equal(torch.stack(steps, 1).cpu().numpy(), ref_steps)
     m.set_option("decode_contexts", 4)                   # allowed again once the state is closed
+
+
+def test_every_graph_kind_keeps_its_own_graphs():
+    """The eight kinds of captured decode step — {plain, token log-probs} x {greedy, sampled} x {no rules, a
+    suppressed token} — each own a slot per decode context: walking them in one order, then in the reverse order,
+    re-captures nothing and returns the same ids (and log-probs), so no kind evicts or replays another's graphs;
+    10 steps at steps_per_graph = 8 replay both the 8-step and the 1-step graph. Changing steps_per_graph drops
+    them all: the next call captures again."""
+    dims = get_dims("micro")
+    m = WhisperCB.from_state_dict(dims, make_weights(dims, seed=0, recipe="margin"), dtype="f32")
+    x = torch.from_numpy(W.log_mel(synth_batch(2), dims.n_mel))
+    kinds = [dict(output_logprobs=lp, **smp, **rules)
+             for rules in ({}, {"suppress_tokens": [5]})
+             for smp in ({}, {"temperature": 1.0, "seed": 5})
+             for lp in (False, True)]
+
+    def walk(order):
+        out = {}
+        for i in order:
+            for _ in range(2):   # once per decode context
+                r = m.generate(x, max_length=10, min_new_tokens=10, return_dict_in_generate=True, **kinds[i])
+                out.setdefault(i, []).append((r.sequences.cpu(), r.token_logprobs.cpu() if kinds[i]["output_logprobs"] else None))
+        return out
+
+    first = walk(range(8))
+    captures = m.debug_counter("graph_captures")
+    assert captures == 8 * 2 * 2   # kinds x contexts x (1-step, 8-step)
+    second = walk(reversed(range(8)))
+    assert m.debug_counter("graph_captures") == captures
+    for i in range(8):
+        for (s0, l0), (s1, l1) in zip(first[i], second[i]):
+            assert torch.equal(s0, s1), (kinds[i], s0, s1)
+            assert (l0 is None and l1 is None) or torch.equal(l0, l1), (kinds[i], l0, l1)
+    m.set_option("steps_per_graph", 4)
+    m.generate(x, max_length=10, min_new_tokens=10)
+    assert m.debug_counter("graph_captures") > captures

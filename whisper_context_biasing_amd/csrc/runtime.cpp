@@ -138,6 +138,22 @@ struct ForestDev {
   const int *trans_off = nullptr, *trans_tok = nullptr, *trans_dst = nullptr, *st_depth = nullptr, *st_keep = nullptr;
 };
 
+// One decode: its shape and what its selection needs. The step-wise API hands it out as its state (one active per
+// handle, on decode context kMaxCtx-1); wcb_generate* keeps one on its stack for the length of the call.
+struct wcb_state {
+  wcb_handle* h = nullptr;
+  int B = 0, P = 1, T = 0, steps = 0, max_new = 0, min_new = 0, xmode = 1;
+  int fwd = 0;   // positions appended by wcb_forward_cached (a forward-cache state takes no decode steps)
+  float lam = 0.f;
+  uint64_t bias_id = 0;
+  int nb = 1;    // beams per utterance (> 1: beam search, rows R = B·nb; the running beams in bm)
+  BeamArgs bm;
+  bool forest = false;   // per-utterance lists installed (wcb_decode_bias_batch): every step takes bias = NULL
+  ForestDev fd;
+  bool logprobs = false; // wcb_decode_enable_logprobs: every step also writes its column of the context's lpbuf
+  bool sampling = false; // wcb_decode_enable_sampling: every step draws its tokens (the context's samp words)
+};
+
 // lean decode projection classes stamped inside the replayed decode graph (stamps pass), by region
 static const char* const kLeanStampClass[] = {"dec_xattn", "dec_qkv", "dec_out", "dec_xq", "dec_xo", "dec_fc1", "dec_fc2",
                                               "dec_kq"};
@@ -146,6 +162,20 @@ static int lean_stamp_region(const char* cls) {
     if (!strcmp(cls, kLeanStampClass[r])) return r;
   return 0;
 }
+
+// The captured decode step of one kind of call: one step, and steps_per_graph consecutive steps in one graph
+// (null when that is 1), with the key naming everything the capture baked in
+struct StepGraphs {
+  hipGraphExec_t one = nullptr, k = nullptr;
+  std::string key;
+  void drop() {
+    for (hipGraphExec_t* g : {&one, &k}) {
+      if (*g) (void)hipGraphExecDestroy(*g);
+      *g = nullptr;
+    }
+    key.clear();
+  }
+};
 
 // Decode state of one in-flight generate call. Two contexts (one per cross-K/V buffer) let call
 // i+1 decode on its own stream while call i is still decoding: two latency-bound step chains share
@@ -160,43 +190,24 @@ struct DecCtx {
       pids, outbuf, forced, beam;
   DevBuf kq_cnt;   // 64-bit arrival counters of the fused xq+kq launches [L][kMaxSub][4 row blocks][H] (monotonic)
   int nchunk = 64;
-  hipGraphExec_t gexec = nullptr;               // captured decode step
-  hipGraphExec_t gexec_k = nullptr;             // steps_per_graph consecutive decode steps in one graph
   int* done_h = nullptr;                        // pinned: the "all rows finished" step of the last 2 chunks
   hipEvent_t ev_poll[2] = {};
-  std::string gkey;
   // token log-probs (wcb_generate_scored, wcb_decode_enable_logprobs): the LM head's softmax partials
   // [rows][nchunk] beside part_val, the log-prob rows [rows][out_ld] beside outbuf — allocated by the first
-  // scored call — and the scored decode's own graphs, so scored and unscored calls each replay theirs
+  // scored call
   DevBuf part_max, part_sum, lpbuf;
-  hipGraphExec_t gexec_lp = nullptr, gexec_k_lp = nullptr;
-  std::string gkey_lp;
   // temperature sampling (wcb_generate_sampled, wcb_decode_enable_sampling): samp = one 64-bit word holding
   // the bits of inv_T = 1 / T in its low half, then the per-row seeds [64] — written on the decode stream at
   // the start of every sampled call, read by the sampled kernels through this stable address, so the
-  // sampled decode's own graphs ([0] without, [1] with token log-probs) hold for every seed and temperature
+  // sampled graphs hold for every seed and temperature
   DevBuf samp;
-  hipGraphExec_t gexec_sm[2] = {}, gexec_k_sm[2] = {};
-  std::string gkey_sm[2];
-  // token rules (wcb_set_token_rules): a ruled decode's own graphs beside the four kinds above ([0] plain, [1]
-  // with token log-probs, [2] / [3] sampled without / with them), so ruled and unruled calls each replay theirs
-  hipGraphExec_t gexec_tr[4] = {}, gexec_k_tr[4] = {};
-  std::string gkey_tr[4];
+  // the captured decode steps, one slot per kind of call: a ruled (wcb_set_token_rules), a sampled and a scored
+  // (token log-probs) decode each launch other kernels or arguments, so every combination replays its own graphs
+  // and no kind of call evicts another's
+  StepGraphs graphs[8];
+  StepGraphs& graphs_of(bool ruled, bool sampled, bool scored) { return graphs[4 * ruled + 2 * sampled + scored]; }
   void drop_graphs() {
-    for (hipGraphExec_t* g : {&gexec, &gexec_k, &gexec_lp, &gexec_k_lp, &gexec_sm[0], &gexec_sm[1], &gexec_k_sm[0],
-                              &gexec_k_sm[1], &gexec_tr[0], &gexec_tr[1], &gexec_tr[2], &gexec_tr[3], &gexec_k_tr[0],
-                              &gexec_k_tr[1], &gexec_k_tr[2], &gexec_k_tr[3]}) {
-      if (*g) (void)hipGraphExecDestroy(*g);
-      *g = nullptr;
-    }
-    gkey.clear();
-    gkey_lp.clear();
-    gkey_sm[0].clear();
-    gkey_sm[1].clear();
-    for (std::string& k : gkey_tr) k.clear();
-  }
-  std::string all_gkeys() const {
-    return gkey + gkey_lp + gkey_sm[0] + gkey_sm[1] + gkey_tr[0] + gkey_tr[1] + gkey_tr[2] + gkey_tr[3];
+    for (StepGraphs& g : graphs) g.drop();
   }
   // per-utterance bias forest of the call decoding in this context: device buffer carved by the capacities
   // (states, transitions, root children; they only grow: quiesce + realloc, the graph key names them), the
@@ -1229,6 +1240,16 @@ void encode_impl(wcb_handle* h, const float* mel, int B, void* enc_out) {
 // device ints of a decode context: I_TU = the greedy select's 64-bit arrival | unfinished counter (8-byte aligned)
 enum { I_STEP = 0, I_POS = 1, I_DONE = 2, I_TICKET = 3, I_UNFIN = 4, I_TU = 6, I_NEXT = 16 };
 
+// the per-row ints of a decode of R rows, behind I_NEXT: [R] each, ts_state [R][2] (token rules: the timestamp
+// grammar's row state, read by the ruled greedy finalize alone)
+struct RowInts {
+  int *next, *state, *finished, *rowbase, *ts_state;   // input ids, automaton state, finished flag, k - d of the state
+  RowInts(const DecCtx& D, int R)
+      : next(D.ints.as<int>() + I_NEXT), state(next + R), finished(next + 2 * R), rowbase(next + 3 * R), ts_state(next + 4 * R) {}
+  // the int block of R rows: what ensure_dec_ws allocates (+ 16 of slack) and the start of a decode zeroes
+  static size_t words(int R) { return I_NEXT + 6 * (size_t)R; }
+};
+
 void drop_graphs(wcb_handle* h) {
   for (DecCtx& D : h->dc) D.drop_graphs();
 }
@@ -1236,6 +1257,8 @@ void drop_graphs(wcb_handle* h) {
 // positions per prefill pass: up to kPrefillRows activation rows (bounds the row workspaces)
 constexpr int kPrefillRows = 256;
 int prefill_chunk(int R) { return std::max(1, kPrefillRows / std::max(R, 1)); }
+// activation rows of a decode of R rows whose prefill carries n positions (none: its steps' R rows)
+int prefill_rows(int R, int n) { return n > 0 ? R * std::min(prefill_chunk(R), n) : R; }
 
 // decode workspace: B decoder rows (clips x beams) reading `clips` encoder outputs; activation
 // buffers for `rows` >= B rows (a prefill pass carries several positions per decoder row)
@@ -1270,7 +1293,7 @@ void ensure_dec_ws(wcb_handle* h, int clips, int B, int T, int out_ld, int xmode
   const DecCtx& D0 = h->dc[c1 - 1];   // every context of the range is sized together
   const size_t xbuf = xmode ? (size_t)xenc_fm_elems(clips, (int)S, (int)d) * e : 2 * L * (size_t)clips * S * d * e;
   const size_t need[] = {xbuf, 2 * L * (size_t)B * T * d * e, (size_t)rows * d * 4,
-                         (size_t)rows * h->d.ffn * e, (size_t)B * h->vocab_pad * 4, (size_t)(I_NEXT + 6 * B + 16) * 4,
+                         (size_t)rows * h->d.ffn * e, (size_t)B * h->vocab_pad * 4, (RowInts::words(B) + 16) * 4,
                          (size_t)B * out_ld * 4};
   const DevBuf* have[] = {&h->xkv2[c1 - 1], &D0.kvself, &D0.dx, &D0.dffn, &D0.logits, &D0.ints, &D0.outbuf};
   bool grow = false;
@@ -1316,7 +1339,7 @@ void ensure_lp_ws(wcb_handle* h, DecCtx& D, int B, int out_ld) {
   const size_t np = (size_t)std::max(B, D.dec_B) * D.nchunk * 4, nl = (size_t)B * out_ld * 4;
   if (np <= D.part_max.bytes && np <= D.part_sum.bytes && nl <= D.lpbuf.bytes) return;
   quiesce(h);
-  D.drop_graphs();
+  if (D.part_max.p || D.lpbuf.p) D.drop_graphs();   // (the first allocation frees nothing a graph could hold)
   D.part_max.ensure(np);
   D.part_sum.ensure(np);
   D.lpbuf.ensure(nl);
@@ -1345,12 +1368,29 @@ void fill_xenc(wcb_handle* h, int buf, const void* src, int B, hipStream_t st) {
   }
 }
 
+// Encoder state into decode context `buf` from the encoder output `enc` ([B][1500][d]: the caller's, or the encoder
+// run just done): the copy the encoder-space kernel streams (xm 1, on st) or the cross-K/V GEMM (xm 0, always on the
+// encoder stream). st = the encoder stream (a pipelined context, whose ev_dec[buf] it already waits for): ev_xkv[buf]
+// is recorded for the decode stream. st = the step-wise context's own stream, which no event orders after the GEMM:
+// that waits for the caller's stream, and the encoder stream is drained.
+void enc_to_ctx(wcb_handle* h, int buf, const void* enc, int B, int xm, hipStream_t st, void* caller_stream) {
+  const bool piped = st == h->he;
+  if (xm == 1) {
+    fill_xenc(h, buf, enc, B, st);
+  } else {
+    if (!piped) sync_in(h, caller_stream, h->he);
+    cross_kv(h, B, buf, enc);
+    if (!piped) HIPCHK(hipStreamSynchronize(h->he));
+  }
+  if (piped) HIPCHK(hipEventRecord(h->ev_xkv[buf], h->he));
+}
+
 struct StepCfg {
-  int B, T, out_ld, buf;   // B: decoder rows (clips x beams); buf: which cross-K/V buffer the step reads
-  bool lm_head, select;
-  float* logits_out; long logits_ld;   // LM head destination
-  const wcb_bias* bias; float lam; int min_new;
-  const int* forced; int forced_ld;    // advance_forced source when !select
+  int B = 0, T = 0, out_ld = 0, buf = 0;   // B: decoder rows (clips x beams); buf: which cross-K/V buffer the step reads
+  bool lm_head = false, select = false;
+  float* logits_out = nullptr; long logits_ld = 0;   // LM head destination
+  const wcb_bias* bias = nullptr; float lam = 0.f; int min_new = 0;
+  const int* forced = nullptr; int forced_ld = 0;    // advance_forced source when !select
   int clips = 0, nb = 1;               // encoder outputs (0: B) and decoder rows per encoder output
   int xmode = 1;                       // cross-attention formulation of this call (wcb_handle::xmode)
   int host_pos = -1;                   // decoder position of this step when known on the host (eager)
@@ -1385,6 +1425,29 @@ struct AlignPass {
   int P = 1, nrow = 0, pos0 = 0, clip0 = 0, nclip = 0;
   float* w = nullptr;   // [nclip][heads_total][nrow][S]
 };
+
+// what every pass over `rows` decoder rows in context buf starts from: the context's logits rows as the LM head's
+// destination, no bias list, the handle's cross-attention formulation; the caller names the rest
+StepCfg step_cfg(wcb_handle* h, int buf, int rows, int T, int out_ld) {
+  StepCfg c;
+  c.B = rows; c.T = T; c.out_ld = out_ld; c.buf = buf;
+  c.logits_out = h->dc[buf].logits.as<float>(); c.logits_ld = h->vocab_pad;
+  c.bias = h->empty_bias.get();
+  c.xmode = h->xmode;
+  return c;
+}
+
+// the bias automaton a selection walks into its arguments (SelectArgs / BeamArgs): the shared one, then — per-utterance
+// lists — the forest's state space in its place, the clip's root children per row (the root bitmap stays bs's)
+template <typename Args>
+void set_automaton(Args& a, const wcb_bias* bs, const ForestDev* F) {
+  a.root_bits = bs->root_bits.as<uint32_t>(); a.root_child = bs->root_child.as<int>();
+  a.trans_off = bs->trans_off.as<int>(); a.trans_tok = bs->trans_tok.as<int>(); a.trans_dst = bs->trans_dst.as<int>();
+  a.st_depth = bs->st_depth.as<int>(); a.st_keep = bs->st_keep.as<int>();
+  if (!F) return;
+  a.trans_off = F->trans_off; a.trans_tok = F->trans_tok; a.trans_dst = F->trans_dst;
+  a.st_depth = F->st_depth; a.st_keep = F->st_keep; a.forest = F->f;
+}
 
 // the handle's token rules into a greedy step configuration
 void apply_rules(const wcb_handle* h, StepCfg& c) {
@@ -1698,7 +1761,7 @@ void decode_rows(wcb_handle* h, const StepCfg& c, int b0, int nb, int chain, hip
       lm.sel_val = D.part_val.as<float>() + (size_t)b0 * D.nchunk;
       lm.sel_idx = D.part_idx.as<int>() + (size_t)b0 * D.nchunk;
       lm.sel_root_bits = c.bias->root_bits.as<uint32_t>(); lm.sel_lam = c.lam;
-      lm.sel_rowbase = ints + I_NEXT + 3 * c.B + b0;   // per row k - d of its state (select_finalize)
+      lm.sel_rowbase = RowInts(D, c.B).rowbase + b0;   // per row k - d of its state (select_finalize)
       lm.sel_eos = h->d.eos_token_id; lm.sel_step = ints + I_STEP; lm.sel_min_new = c.min_new;
       if (c.logprob_out) {   // token log-probs: the softmax partials of the raw logits beside the argmax ones
         lm.sel_max = D.part_max.as<float>() + (size_t)b0 * D.nchunk;
@@ -1730,7 +1793,7 @@ void step_embed(wcb_handle* h, const StepCfg& c) {
   int* ints = D.ints.as<int>();
   const bool r32 = h->dec_gemm && lnf_possible(h);   // 32-column stats for the folded LayerNorm (rows > 64)
   h->timed("dec_embed", 0, (double)B * d * (2.0 * esize(h->d.dtype) + 4), D.hs, [&] {
-    embed(h->dt, h->tok_emb, h->dec_pos, ints + I_NEXT, ints + I_POS, D.dx.as<float>(),
+    embed(h->dt, h->tok_emb, h->dec_pos, RowInts(D, B).next, ints + I_POS, D.dx.as<float>(),
           !h->dec_gemm ? D.dstats.as<float>() : r32 ? D.drst.as<float>() : nullptr, B, d, D.hs, D.dx16.p, h->d.vocab, 1,
           r32 ? 32 : 16, xfm_possible(h) ? D.dx16fm.p : nullptr);
   });
@@ -1741,7 +1804,7 @@ void decode_step(wcb_handle* h, const StepCfg& c) {
   const int d = h->d.d_model, B = c.B;
   int* ints = D.ints.as<int>();
   int* pos = ints + I_POS;
-  int* next_ids = ints + I_NEXT;
+  const RowInts ri(D, B);
   if (!c.embedded) step_embed(h, c);
   // rows per chain: the skinny projections split rows over grid.y, so a chain can take any number
   // of rows (WCB_GROUP_ROWS; more chains overlap latency, fewer re-read the weights less often)
@@ -1768,17 +1831,10 @@ void decode_step(wcb_handle* h, const StepCfg& c) {
     SelectArgs s;
     s.logits = c.logits_out; s.ld = c.logits_ld; s.M = B; s.V = h->d.vocab;
     s.lam = c.lam;
-    s.root_bits = c.bias->root_bits.as<uint32_t>();
-    s.trans_off = c.bias->trans_off.as<int>(); s.trans_tok = c.bias->trans_tok.as<int>();
-    s.trans_dst = c.bias->trans_dst.as<int>(); s.root_child = c.bias->root_child.as<int>();
-    s.st_depth = c.bias->st_depth.as<int>(); s.st_keep = c.bias->st_keep.as<int>();
-    if (c.forest) {   // per-utterance lists: the forest's state space, the clip's root children per row
-      s.trans_off = c.forest->trans_off; s.trans_tok = c.forest->trans_tok; s.trans_dst = c.forest->trans_dst;
-      s.st_depth = c.forest->st_depth; s.st_keep = c.forest->st_keep; s.forest = c.forest->f;
-    }
-    s.state = next_ids + B; s.finished = next_ids + 2 * B; s.rowbase = next_ids + 3 * B;
+    set_automaton(s, c.bias, c.forest);
+    s.state = ri.state; s.finished = ri.finished; s.rowbase = ri.rowbase;
     s.eos = h->d.eos_token_id; s.pad = h->d.pad_token_id; s.min_new = c.min_new;
-    s.step = ints + I_STEP; s.pos = pos; s.next_ids = next_ids;
+    s.step = ints + I_STEP; s.pos = pos; s.next_ids = ri.next;
     s.out_ids = D.outbuf.as<int>(); s.out_ld = c.out_ld;
     s.part_val = D.part_val.as<float>(); s.part_idx = D.part_idx.as<int>(); s.nchunk = D.nchunk;
     s.all_done = ints + I_DONE;
@@ -1788,7 +1844,7 @@ void decode_step(wcb_handle* h, const StepCfg& c) {
       s.part_max = D.part_max.as<float>(); s.part_sum = D.part_sum.as<float>(); s.out_logprob = c.logprob_out;
     }
     if (c.samp) { s.inv_t = reinterpret_cast<const float*>(c.samp); s.seeds = c.samp + 1; }
-    s.deny = c.deny; s.deny0 = c.deny0; s.ts = c.ts; s.ts_state = next_ids + 4 * B;
+    s.deny = c.deny; s.deny0 = c.deny0; s.ts = c.ts; s.ts_state = ri.ts_state;
     if (c.embedded) {   // the next step's input embedding in the same launch (embed()'s outputs)
       const bool r32 = h->dec_gemm && lnf_possible(h);
       s.emb = h->tok_emb; s.pemb = h->dec_pos; s.n_pos = h->d.n_text_ctx; s.d = d; s.dtype = h->dt;
@@ -1803,7 +1859,7 @@ void decode_step(wcb_handle* h, const StepCfg& c) {
     }
     h->timed("dec_select", 0, (double)B * D.nchunk * 8, D.hs, [&] { select_finalize(s, D.hs); });
   } else {
-    advance_forced(next_ids, c.forced, B, c.forced_ld, pos, D.hs);
+    advance_forced(ri.next, c.forced, B, c.forced_ld, pos, D.hs);
   }
 }
 
@@ -1847,15 +1903,6 @@ void ensure_beam_buf(wcb_handle* h, DecCtx& D, int B, int nb, int Lg, int Tc) {
   beam_words(B, nb, Lg, Tc, w);
   for (size_t x : w) bytes += (x * 4 + 255) / 256 * 256;
   if (bytes > D.beam.bytes) { quiesce(h); D.beam.ensure(bytes); }
-}
-void beam_set_bias(BeamArgs& bm, const wcb_bias* bs) {
-  bm.root_bits = bs->root_bits.as<uint32_t>(); bm.root_child = bs->root_child.as<int>();
-  bm.trans_off = bs->trans_off.as<int>(); bm.trans_tok = bs->trans_tok.as<int>(); bm.trans_dst = bs->trans_dst.as<int>();
-  bm.st_depth = bs->st_depth.as<int>(); bm.st_keep = bs->st_keep.as<int>();
-}
-void beam_set_forest(BeamArgs& bm, const ForestDev& F) {
-  bm.trans_off = F.trans_off; bm.trans_tok = F.trans_tok; bm.trans_dst = F.trans_dst;
-  bm.st_depth = F.st_depth; bm.st_keep = F.st_keep; bm.forest = F.f;
 }
 
 // Per-utterance bias forest of a decode in context D: the host forest copied into the context's device
@@ -1953,7 +2000,6 @@ BeamArgs beam_args(wcb_handle* h, DecCtx& D, int B, int nb, int P, int Lt, int T
   beam_words(B, nb, Lg, Tc, w);
   char* p = (char*)D.beam.p;
   auto take = [&](int i) { char* q = p; p += (w[i] * 4 + 255) / 256 * 256; return q; };
-  const int R = B * nb;
   int* ints = D.ints.as<int>();
   BeamArgs bm;
   bm.run_sc = (float*)take(0); bm.fin_sc = (float*)take(1); bm.fin_done = (int*)take(2); bm.fin_len = (int*)take(3);
@@ -1965,11 +2011,118 @@ BeamArgs beam_args(wcb_handle* h, DecCtx& D, int B, int nb, int P, int Lt, int T
   bm.B = B; bm.nb = nb; bm.K = 2 * nb; bm.P = P; bm.Lt = Lt; bm.T = Tc;
   bm.eos = h->d.eos_token_id; bm.pad = h->d.pad_token_id; bm.min_new = min_new;
   bm.lam = lam; bm.len_pen = 1.f;
-  beam_set_bias(bm, bs);
+  set_automaton(bm, bs, nullptr);
   bm.step = ints + I_STEP; bm.pos = ints + I_POS; bm.all_done = ints + I_DONE; bm.ticket = ints + I_TICKET;
-  bm.next_ids = ints + I_NEXT; bm.state = ints + I_NEXT + R;
+  const RowInts ri(D, B * nb);
+  bm.next_ids = ri.next; bm.state = ri.state;
   bm.out_ids = D.outbuf.as<int>(); bm.out_ld = Lg; bm.out_len = ints + I_UNFIN;
   return bm;
+}
+
+// Causal prefill of positions [p_begin, p_end) of every row (ids from src, row stride ld: prefill_step), in passes
+// of prefill_chunk(rows) positions; each(c, p0, np) names what a pass's configuration has of its own
+template <typename F>
+void prefill_range(wcb_handle* h, const StepCfg& sc, const int* src, int ld, int p_begin, int p_end, F&& each) {
+  for (int p0 = p_begin, np; p0 < p_end; p0 += np) {
+    np = std::min(prefill_chunk(sc.B), p_end - p0);
+    StepCfg c = sc;
+    each(c, p0, np);
+    prefill_step(h, c, np, src, ld);
+  }
+}
+void prefill_range(wcb_handle* h, const StepCfg& sc, const int* src, int ld, int p_begin, int p_end) {
+  prefill_range(h, sc, src, ld, p_begin, p_end, [](StepCfg&, int, int) {});
+}
+
+// The start of decode `st` in context buf, on its stream: the int block zeroed, the prompt uploaded — `shared`: one
+// host row [P] for every decoder row (row stride 0), else [B][P], clip b's on each of its beam rows; null: the
+// start token — the beam state initialised (before the prefill: its self-attention reads keys through bm.phys),
+// and the configuration every pass of the decode starts from
+StepCfg decode_start(wcb_handle* h, int buf, wcb_state& st, const int32_t* prefix, bool shared, const wcb_bias* bs) {
+  DecCtx& D = h->dc[buf];
+  const int R = st.B * st.nb, P = st.P;
+  HIPCHK(hipMemsetAsync(D.ints.p, 0, RowInts::words(R) * 4, D.hs));   // (the rule state with finished[])
+  std::vector<int32_t> rows;
+  if (prefix && !shared)
+    for (int r = 0; r < R; ++r) rows.insert(rows.end(), prefix + (size_t)(r / st.nb) * P, prefix + (size_t)(r / st.nb + 1) * P);
+  const size_t pbytes = (shared ? (size_t)P : rows.size()) * 4;
+  if (prefix && pbytes > D.forced.bytes) { quiesce(h); D.forced.ensure(pbytes); }
+  if (!prefix) {
+    fill_i32(RowInts(D, R).next, h->d.decoder_start_token_id, R, D.hs);
+  } else if (shared) {
+    write_i32(D.forced.as<int>(), prefix, P, D.hs);
+  } else {
+    HIPCHK(hipMemcpyAsync(D.forced.p, rows.data(), pbytes, hipMemcpyHostToDevice, D.hs));
+    HIPCHK(hipStreamSynchronize(D.hs));   // pageable host source
+  }
+  if (st.nb > 1) {
+    st.bm = beam_args(h, D, st.B, st.nb, P, P + st.max_new, st.T, st.max_new, st.min_new, st.lam, bs);
+    beam_init(st.bm, D.hs);
+  }
+  StepCfg sc = step_cfg(h, buf, R, st.T, st.max_new);
+  sc.bias = bs; sc.lam = st.lam; sc.min_new = st.min_new;
+  sc.forced = D.forced.as<int>(); sc.forced_ld = shared ? 0 : P;
+  sc.clips = st.B; sc.nb = st.nb; sc.xmode = st.xmode;
+  if (st.nb > 1) { sc.phys = st.bm.phys; sc.beam = &st.bm; }
+  return sc;
+}
+
+// The prompt of a decode begun by decode_start: positions 0 .. P-2 in causal prefill passes, then the last prompt
+// token as the first step's input — greedy: embedded here, every step's finalize then embeds the next one
+void decode_prompt(wcb_handle* h, const StepCfg& sc, int P, bool has_prefix) {
+  DecCtx& D = h->dc[sc.buf];
+  prefill_range(h, sc, sc.forced, sc.forced_ld, 0, P - 1);
+  if (has_prefix) gather_col(RowInts(D, sc.B).next, sc.forced, sc.B, sc.forced_ld, P - 1, D.hs);
+  if (sc.nb == 1) step_embed(h, sc);
+}
+
+// per-utterance lists into decode `st` of context D, before its first step: the forest uploaded, every row in its
+// clip's root state
+void start_forest(wcb_handle* h, DecCtx& D, wcb_state& st, const wcb_bias_batch* bb) {
+  const int R = st.B * st.nb;
+  const RowInts ri(D, R);
+  st.fd = install_forest(h, D, bb);
+  forest_init(st.fd.f, ri.state, st.nb == 1 ? ri.rowbase : nullptr, R, st.nb, D.hs);
+  st.forest = true;
+}
+
+// The decode step of sc captured into g under `key`: the 1-step graph and, when it differs, the graph of
+// steps_per_graph consecutive steps (every position-dependent value is read on the device, so it is the
+// single-step graph unrolled)
+void capture_steps(wcb_handle* h, const StepCfg& sc, StepGraphs& g, const char* key) {
+  DecCtx& D = h->dc[sc.buf];
+  g.drop();
+  const int ks[2] = {1, h->steps_per_graph};
+  hipGraphExec_t* const exec[2] = {&g.one, &g.k};
+  for (int ki = 0; ki < (ks[1] > 1 ? 2 : 1); ++ki) {
+    hipGraph_t graph;
+    HIPCHK(hipStreamBeginCapture(D.hs, hipStreamCaptureModeThreadLocal));
+    for (int i = 0; i < ks[ki]; ++i) decode_step(h, sc);
+    HIPCHK(hipStreamEndCapture(D.hs, &graph));
+    HIPCHK(hipGraphInstantiate(exec[ki], graph, nullptr, nullptr, 0));
+    ++h->n_graph_captures;
+    HIPCHK(hipGraphDestroy(graph));
+  }
+  g.key = key;
+}
+
+// One wcb_generate* call: batch, prompt, outputs, then what only some entry points have — bias, scores, sampling.
+// Null: prefix (the start token alone), bias / bb (no shared automaton / per-utterance forest), smp (argmax)
+struct GenCall {
+  const float* mel; int B; const wcb_gen_cfg* cfg;
+  const int32_t* prefix; int prefix_len;
+  int32_t *out_ids, *out_steps;
+  void* stream;
+  const wcb_bias* bias = nullptr; const wcb_bias_batch* bb = nullptr;
+  float *out_logprobs = nullptr, *out_seq_scores = nullptr;
+  const wcb_sample_cfg* smp = nullptr;
+};
+
+// the step-wise decode context, after the check every step-wise entry point makes of its state (`what`: the
+// entry's other required arguments are there; `msg`: its own wording of the refusal)
+DecCtx& step_ctx(wcb_handle* h, const wcb_state* st, bool what = true, const char* msg = "bad argument (state of this handle)") {
+  REQUIRE(h && st && st->h == h && h->step_state == st && what, msg);
+  return h->dc[wcb_handle::kMaxCtx - 1];
 }
 
 }  // namespace
@@ -2003,13 +2156,14 @@ int wcb_encode(wcb_handle* h, const float* mel, int B, void* enc_out, void* stre
   });
 }
 
-// wcb_generate / wcb_generate_biased: one shared automaton `bias` (or none), or the per-utterance forest `bb`
-static void generate_impl(wcb_handle* h, const float* mel, int B, const wcb_gen_cfg* cfg, const wcb_bias* bias,
-                          const wcb_bias_batch* bb, const int32_t* prefix, int prefix_len, int32_t* out_ids,
-                          int32_t* out_steps, void* stream, float* out_logprobs = nullptr, float* out_seq_scores = nullptr,
-                          const wcb_sample_cfg* smp = nullptr) {
+// every wcb_generate* entry point: encode, then decode greedily or by beam search
+static void generate_impl(wcb_handle* h, const GenCall& c) {
   {
-    REQUIRE(h && cfg && out_ids && out_steps && B > 0, "bad argument");
+    const wcb_gen_cfg* cfg = c.cfg;
+    const wcb_sample_cfg* smp = c.smp;
+    const wcb_bias_batch* bb = c.bb;
+    const int B = c.B;
+    REQUIRE(h && cfg && c.out_ids && c.out_steps && B > 0, "bad argument");
     if (!h->ready) throw WcbError(WCB_ERR_STATE, "weights not finalized");
     const int nb = cfg->num_beams;
     REQUIRE(nb >= 1 && nb <= kMaxBeams, "num_beams must be in [1, 8]");
@@ -2021,21 +2175,21 @@ static void generate_impl(wcb_handle* h, const float* mel, int B, const wcb_gen_
       throw WcbError(WCB_ERR_UNSUPPORTED, "token rules are greedy only (num_beams = 1; wcb_set_token_rules(h, NULL) removes them)");
     if (h->rules_on && h->rules_ts.on && smp)
       throw WcbError(WCB_ERR_UNSUPPORTED, "timestamp decoding with sampling is not supported (greedy only)");
-    if (nb > 1 && out_logprobs)
+    if (nb > 1 && c.out_logprobs)
       throw WcbError(WCB_ERR_UNSUPPORTED, "token log-probs are greedy only (beam search: out_seq_scores)");
-    if (nb == 1 && out_seq_scores)
+    if (nb == 1 && c.out_seq_scores)
       throw WcbError(WCB_ERR_UNSUPPORTED, "sequence scores are beam-search only (greedy: out_logprobs)");
     const int R = B * nb;   // decoder rows: utterance b, beam i -> row b*nb + i
     REQUIRE(B <= 64, "batch > 64 per handle: split the batch");
     REQUIRE(R <= 64 * DecCtx::kMaxSub, "batch x num_beams > 512 rows per call: split the batch");
     REQUIRE(cfg->bias_boost >= 0.f, "bias_boost must be >= 0");
     REQUIRE(cfg->max_new_tokens >= 1, "max_new_tokens must be >= 1");
-    REQUIRE(mel != nullptr, "mel is required");
-    const int P = prefix ? prefix_len : 1;
+    REQUIRE(c.mel != nullptr, "mel is required");
+    const int P = c.prefix ? c.prefix_len : 1;
     REQUIRE(P >= 1, "prefix_len must be >= 1");
     const int T = P + cfg->max_new_tokens;
     REQUIRE(T <= h->d.n_text_ctx + 1, "prefix + max_new_tokens exceeds max_target_positions");
-    const wcb_bias* bs = bias ? bias : h->empty_bias.get();
+    const wcb_bias* bs = c.bias ? c.bias : h->empty_bias.get();
     REQUIRE(bs == h->empty_bias.get() || bs->owner == h,
             "bias automaton was created on another handle (wcb_bias_create binds it to its handle)");
     REQUIRE(bs->vocab == h->d.vocab, "bias automaton built for another vocabulary");
@@ -2044,82 +2198,57 @@ static void generate_impl(wcb_handle* h, const float* mel, int B, const wcb_gen_
       REQUIRE(bb->B == B, "bias batch: built for " + std::to_string(bb->B) + " clips, the call has " + std::to_string(B));
     }
     const bool fixed_len = cfg->min_new_tokens >= cfg->max_new_tokens;   // EOS masked: no host polling
-    const int out_ld = cfg->max_new_tokens;
+    const int max_new = cfg->max_new_tokens, out_ld = max_new;
     const int Tc = std::min(T, h->d.n_text_ctx);
     if (nb > 1) {
-      REQUIRE(cfg->max_new_tokens <= kBeamMaxLen && Tc <= kBeamMaxLen, "beam search: more than 448 positions");
+      REQUIRE(max_new <= kBeamMaxLen && Tc <= kBeamMaxLen, "beam search: more than 448 positions");
       REQUIRE(cfg->bias_boost == 0.f || h->d.vocab <= kBeamMaxVocab, "beam search boost: vocabulary too large");
     }
     ensure_enc_ws(h, B);
     const int xm = nb > 1 ? h->beam_xmode : h->xmode;   // this call's cross-attention formulation
-    ensure_dec_ws(h, B, R, Tc, out_ld, xm, P > 1 ? R * std::min(prefill_chunk(R), P - 1) : R);
+    ensure_dec_ws(h, B, R, Tc, out_ld, xm, prefill_rows(R, P - 1));
     const int buf = h->gen_count++ % h->nctx;
     h->last_gen_buf = buf; h->last_gen_B = B; h->last_gen_xm = xm; h->last_gen_id = h->gen_count;   // (wcb_align, enc = NULL)
     DecCtx& D = h->dc[buf];
     // beam state [R] / [R][max_new] / [R][Tc] / [R][K] / [B][2] in one buffer
-    if (nb > 1) ensure_beam_buf(h, D, B, nb, cfg->max_new_tokens, Tc);
-    if (out_logprobs) ensure_lp_ws(h, D, R, out_ld);
+    if (nb > 1) ensure_beam_buf(h, D, B, nb, max_new, Tc);
+    if (c.out_logprobs) ensure_lp_ws(h, D, R, out_ld);
     // ---- encoder stream: front end → encoder → cross-K/V into buffer `buf` once the decode that
     //      last read that buffer has finished. It overlaps the previous call's decode.
-    sync_in(h, stream, h->he);
+    sync_in(h, c.stream, h->he);
     HIPCHK(hipStreamWaitEvent(h->he, h->ev_dec[buf], 0));
     if (xm == 1) {   // the decode reads the encoder output itself (re-laid out for the stream when xenc_fm)
-      encode_impl(h, mel, B, xenc_fm_on(h) ? nullptr : h->xkv2[buf].p);
+      encode_impl(h, c.mel, B, xenc_fm_on(h) ? nullptr : h->xkv2[buf].p);
       if (xenc_fm_on(h)) fill_xenc(h, buf, h->encout.p, B, h->he);
     } else {
-      encode_impl(h, mel, B, nullptr);
+      encode_impl(h, c.mel, B, nullptr);
       h->timed_wall("xkv_gemm_total", h->he, [&] { cross_kv(h, B, buf, h->encout.p); });
     }
     HIPCHK(hipEventRecord(h->ev_xkv[buf], h->he));
     // ---- decode stream
     HIPCHK(hipStreamWaitEvent(D.hs, h->ev_xkv[buf], 0));
     int* ints = D.ints.as<int>();
-    HIPCHK(hipMemsetAsync(ints, 0, (size_t)(I_NEXT + 6 * R) * 4, D.hs));   // (the rule state with finished[])
-    if (prefix) {   // one prefix row shared by every decoder row (forced_ld = 0 below)
-      if ((size_t)P * 4 > D.forced.bytes) { quiesce(h); D.forced.ensure((size_t)P * 4); }
-      write_i32(D.forced.as<int>(), prefix, P, D.hs);
-      gather_col(ints + I_NEXT, D.forced.as<int>(), R, 0, 0, D.hs);
-    } else {
-      fill_i32(ints + I_NEXT, h->d.decoder_start_token_id, R, D.hs);
+    wcb_state st;
+    st.h = h; st.B = B; st.nb = nb; st.P = P; st.T = Tc; st.max_new = max_new; st.min_new = cfg->min_new_tokens;
+    st.lam = cfg->bias_boost; st.xmode = xm;
+    StepCfg sc = decode_start(h, buf, st, c.prefix, /*shared=*/true, bs);
+    BeamArgs& bm = st.bm;
+    if (bb) {   // per-utterance lists
+      start_forest(h, D, st, bb);
+      sc.forest = &st.fd;
+      if (nb > 1) set_automaton(bm, bs, &st.fd);
     }
-    BeamArgs bm;
-    if (nb > 1) {
-      bm = beam_args(h, D, B, nb, P, T, Tc, cfg->max_new_tokens, cfg->min_new_tokens, cfg->bias_boost, bs);
-      beam_init(bm, D.hs);   // before the prefill: the self-attention reads keys through bm.phys
-    }
-    ForestDev fd;
-    if (bb) {   // per-utterance lists: upload the forest, every row into its clip's root state
-      fd = install_forest(h, D, bb);
-      forest_init(fd.f, ints + I_NEXT + R, nb == 1 ? ints + I_NEXT + 3 * R : nullptr, R, nb, D.hs);
-      if (nb > 1) beam_set_forest(bm, fd);
-    }
-    StepCfg sc{R, Tc, out_ld, buf, false, false, D.logits.as<float>(), (long)h->vocab_pad, bs, cfg->bias_boost,
-               cfg->min_new_tokens, D.forced.as<int>(), 0};
-    if (bb) sc.forest = &fd;
-    sc.clips = B;
-    sc.nb = nb;
-    sc.xmode = xm;
-    if (nb > 1) { sc.phys = bm.phys; sc.beam = &bm; }
-    if (out_logprobs) {   // every column a step does not reach stays 0
+    if (c.out_logprobs) {   // every column a step does not reach stays 0
       sc.logprob_out = D.lpbuf.as<float>();
       HIPCHK(hipMemsetAsync(D.lpbuf.p, 0, (size_t)R * out_ld * 4, D.hs));
     }
     if (smp) sc.samp = install_sampling(D, smp->temperature, smp->seeds, R);
     const bool ruled = nb == 1 && h->rules_on;
     if (ruled) apply_rules(h, sc);
-    // prompt positions 0 .. P-2 in causal prefill passes, then the last prompt token is the first
-    // decode step's input
-    for (int p0 = 0, np; p0 + 1 < P; p0 += np) {
-      np = std::min(prefill_chunk(R), P - 1 - p0);
-      prefill_step(h, sc, np, D.forced.as<int>(), 0);
-    }
-    if (P > 1) gather_col(ints + I_NEXT, D.forced.as<int>(), R, 0, P - 1, D.hs);
+    decode_prompt(h, sc, P, c.prefix != nullptr);
     sc.lm_head = true;
     sc.select = true;
-    if (nb == 1) {   // greedy: every step's finalize embeds the next step's input; the first one here
-      sc.embedded = true;
-      step_embed(h, sc);
-    }
+    sc.embedded = nb == 1;   // greedy: decode_prompt embedded the first step's input
     // the graph reads a shared automaton through its own buffers (key: its id) and a per-utterance forest
     // through the context's stable buffers (key: forest mode and the capacities, never the lists)
     char key[256], bkey[64];
@@ -2129,38 +2258,16 @@ static void generate_impl(wcb_handle* h, const float* mel, int B, const wcb_gen_
                       cfg->bias_boost, cfg->min_new_tokens, h->n_sub, (int)h->prof_stamps, P);
     if (ruled)   // what a ruled graph bakes in beside the bitmaps' stable addresses
       snprintf(key + kn, sizeof key - kn, "/R%d.%d.%d.%d", sc.ts.on, sc.ts.ts0, sc.ts.max_init, (int)h->rules_has0);
-    const int max_new = cfg->max_new_tokens;
     // per-launch HIP events (profiling bit 0) cannot bracket nodes of a replayed graph: eager launches
     const bool use_graph = cfg->use_graph && !h->prof;
     // The decode step replays as a hipGraph; steps_per_graph steps are captured into one graph so the
-    // per-replay gap is paid once per chunk (every position-dependent value is read on the device, so
-    // a multi-step graph is the single-step graph unrolled). Natural-EOS mode polls the device
-    // "all finished" flag once per chunk.
+    // per-replay gap is paid once per chunk. Natural-EOS mode polls the device "all finished" flag once
+    // per chunk. A ruled, a sampled and a scored decode each replay graphs of their own under the same key
+    // string (never the seeds or the temperature), so no kind of call evicts another's.
     const int chunk = h->steps_per_graph;
     int done = 0, steps = 0;
-    // (a scored decode has its own graphs and key: neither kind of call evicts the other's; so has a sampled
-    // one, without and with log-probs — its key is the same string: never the seeds or the temperature)
-    const int lpi = out_logprobs ? 1 : 0;
-    const int tri = (smp ? 2 : 0) + lpi;   // a ruled decode: its own four kinds
-    hipGraphExec_t& gexec = ruled ? D.gexec_tr[tri] : smp ? D.gexec_sm[lpi] : out_logprobs ? D.gexec_lp : D.gexec;
-    hipGraphExec_t& gexec_k = ruled ? D.gexec_k_tr[tri] : smp ? D.gexec_k_sm[lpi] : out_logprobs ? D.gexec_k_lp : D.gexec_k;
-    std::string& gkey = ruled ? D.gkey_tr[tri] : smp ? D.gkey_sm[lpi] : out_logprobs ? D.gkey_lp : D.gkey;
-    if (use_graph && (!gexec || gkey != key)) {
-      if (gexec) { (void)hipGraphExecDestroy(gexec); gexec = nullptr; }
-      if (gexec_k) { (void)hipGraphExecDestroy(gexec_k); gexec_k = nullptr; }
-      const int ks[2] = {1, chunk};
-      for (int ki = 0; ki < (chunk > 1 ? 2 : 1); ++ki) {   // the k-step graph only when it differs
-        const int k = ks[ki];
-        hipGraph_t graph;
-        HIPCHK(hipStreamBeginCapture(D.hs, hipStreamCaptureModeThreadLocal));
-        for (int i = 0; i < k; ++i) decode_step(h, sc);
-        HIPCHK(hipStreamEndCapture(D.hs, &graph));
-        HIPCHK(hipGraphInstantiate(k == 1 ? &gexec : &gexec_k, graph, nullptr, nullptr, 0));
-        ++h->n_graph_captures;
-        HIPCHK(hipGraphDestroy(graph));
-      }
-      gkey = key;
-    }
+    StepGraphs& g = D.graphs_of(ruled, smp != nullptr, c.out_logprobs != nullptr);
+    if (use_graph && (!g.one || g.key != key)) capture_steps(h, sc, g, key);
     // Natural-EOS mode (reference decoding) polls the device "all finished" step one chunk behind:
     // chunk k+1 is queued before the host waits for chunk k's flag, so the GPU never idles on the
     // host (at most one chunk of extra steps after the last row finished; the output is cut at it).
@@ -2168,12 +2275,12 @@ static void generate_impl(wcb_handle* h, const float* mel, int B, const wcb_gen_
     h->timed_wall("decode_loop", D.hs, [&] {
       while (steps < max_new) {
         const int n = std::min(chunk, max_new - steps);
-        if (use_graph && n == chunk && gexec_k) {
-          HIPCHK(hipGraphLaunch(gexec_k, D.hs));
+        if (use_graph && n == chunk && g.k) {
+          HIPCHK(hipGraphLaunch(g.k, D.hs));
         } else {
           for (int i = 0; i < n; ++i) {
             if (use_graph) {
-              HIPCHK(hipGraphLaunch(gexec, D.hs));
+              HIPCHK(hipGraphLaunch(g.one, D.hs));
             } else {
               sc.host_pos = P - 1 + steps + i;
               decode_step(h, sc);
@@ -2209,13 +2316,13 @@ static void generate_impl(wcb_handle* h, const float* mel, int B, const wcb_gen_
         stamp_reduce(h->stamp_base(buf, r), h->stamp_slots(), h->stamp_acc.as<unsigned long long>() + 2 * r, D.hs);
     }
     if (nb > 1) {   // best finished sequence of every utterance; its columns = the longest of them
-      bm.out_score = out_seq_scores;   // (nullable) that hypothesis's score, straight into the caller's [B]
+      bm.out_score = c.out_seq_scores;   // (nullable) that hypothesis's score, straight into the caller's [B]
       beam_output(bm, D.hs);
-      HIPCHK(hipMemcpyAsync(out_ids, D.outbuf.p, (size_t)B * out_ld * 4, hipMemcpyDeviceToDevice, D.hs));
+      HIPCHK(hipMemcpyAsync(c.out_ids, D.outbuf.p, (size_t)B * out_ld * 4, hipMemcpyDeviceToDevice, D.hs));
       if (cfg->async_out) {   // serving pipelines: every max_new column (pad past each best sequence), no
                               // host wait, so the next call's front end + encoder overlap this decode
         HIPCHK(hipEventRecord(h->ev_dec[buf], D.hs));
-        *out_steps = max_new;
+        *c.out_steps = max_new;
         return;
       }
       int olen = 0;
@@ -2223,34 +2330,34 @@ static void generate_impl(wcb_handle* h, const float* mel, int B, const wcb_gen_
       HIPCHK(hipEventRecord(h->ev_dec[buf], D.hs));
       HIPCHK(hipStreamSynchronize(D.hs));
       if (h->xq_kq) check_dev_err(h);   // the in-launch hand-off's error word: outputs invalid if it is set
-      *out_steps = std::min(olen, max_new);
-      sync_out(h, stream, D.hs);
+      *c.out_steps = std::min(olen, max_new);
+      sync_out(h, c.stream, D.hs);
       return;
     }
-    HIPCHK(hipMemcpyAsync(out_ids, D.outbuf.p, (size_t)B * out_ld * 4, hipMemcpyDeviceToDevice, D.hs));
-    if (out_logprobs)
-      HIPCHK(hipMemcpyAsync(out_logprobs, D.lpbuf.p, (size_t)B * out_ld * 4, hipMemcpyDeviceToDevice, D.hs));
+    HIPCHK(hipMemcpyAsync(c.out_ids, D.outbuf.p, (size_t)B * out_ld * 4, hipMemcpyDeviceToDevice, D.hs));
+    if (c.out_logprobs)
+      HIPCHK(hipMemcpyAsync(c.out_logprobs, D.lpbuf.p, (size_t)B * out_ld * 4, hipMemcpyDeviceToDevice, D.hs));
     HIPCHK(hipEventRecord(h->ev_dec[buf], D.hs));
-    *out_steps = std::min(done, max_new);
+    *c.out_steps = std::min(done, max_new);
     if (!cfg->async_out) {
       // blocking calls with the in-launch hand-off on (option xq_kq) validate its error word before the ids
       // are handed out; async calls report it at wcb_synchronize
       if (h->xq_kq) { HIPCHK(hipStreamSynchronize(D.hs)); check_dev_err(h); }
-      sync_out(h, stream, D.hs);
+      sync_out(h, c.stream, D.hs);
     }
   }
 }
 
 int wcb_generate(wcb_handle* h, const float* mel, int B, const wcb_gen_cfg* cfg, const wcb_bias* bias,
                  const int32_t* prefix, int prefix_len, int32_t* out_ids, int32_t* out_steps, void* stream) {
-  return guarded(h, [&] { generate_impl(h, mel, B, cfg, bias, nullptr, prefix, prefix_len, out_ids, out_steps, stream); });
+  return guarded(h, [&] { generate_impl(h, {mel, B, cfg, prefix, prefix_len, out_ids, out_steps, stream, bias}); });
 }
 
 int wcb_generate_biased(wcb_handle* h, const float* mel, int B, const wcb_gen_cfg* cfg, const wcb_bias_batch* bb,
                         const int32_t* prefix, int prefix_len, int32_t* out_ids, int32_t* out_steps, void* stream) {
   return guarded(h, [&] {
     REQUIRE(bb, "wcb_generate_biased: the bias batch is required (wcb_generate decodes without one)");
-    generate_impl(h, mel, B, cfg, nullptr, bb, prefix, prefix_len, out_ids, out_steps, stream);
+    generate_impl(h, {mel, B, cfg, prefix, prefix_len, out_ids, out_steps, stream, nullptr, bb});
   });
 }
 
@@ -2259,7 +2366,7 @@ int wcb_generate_scored(wcb_handle* h, const float* mel, int B, const wcb_gen_cf
                         float* out_logprobs, float* out_seq_scores, int32_t* out_steps, void* stream) {
   return guarded(h, [&] {
     REQUIRE(!(bias && bb), "wcb_generate_scored: a shared automaton or a bias batch, not both");
-    generate_impl(h, mel, B, cfg, bias, bb, prefix, prefix_len, out_ids, out_steps, stream, out_logprobs, out_seq_scores);
+    generate_impl(h, {mel, B, cfg, prefix, prefix_len, out_ids, out_steps, stream, bias, bb, out_logprobs, out_seq_scores});
   });
 }
 
@@ -2269,7 +2376,7 @@ int wcb_generate_sampled(wcb_handle* h, const float* mel, int B, const wcb_gen_c
   return guarded(h, [&] {
     REQUIRE(smp, "wcb_generate_sampled: the sampling configuration is required (wcb_generate_scored decodes without one)");
     REQUIRE(!(bias && bb), "wcb_generate_sampled: a shared automaton or a bias batch, not both");
-    generate_impl(h, mel, B, cfg, bias, bb, prefix, prefix_len, out_ids, out_steps, stream, out_logprobs, nullptr, smp);
+    generate_impl(h, {mel, B, cfg, prefix, prefix_len, out_ids, out_steps, stream, bias, bb, out_logprobs, nullptr, smp});
   });
 }
 
@@ -2277,82 +2384,42 @@ int wcb_generate_sampled(wcb_handle* h, const float* mel, int B, const wcb_gen_c
 // of wcb_generate, one token per call, on the decode context kMaxCtx-1 (its own stream and buffers,
 // so generate() calls on contexts 0 .. nctx-1 are unaffected); eager launches (the caller inspects
 // every step). One active state per handle.
-struct wcb_state {
-  wcb_handle* h = nullptr;
-  int B = 0, P = 1, T = 0, steps = 0, max_new = 0, min_new = 0, xmode = 1;
-  int fwd = 0;   // positions appended by wcb_forward_cached (a forward-cache state takes no decode steps)
-  float lam = 0.f;
-  uint64_t bias_id = 0;
-  int nb = 1;    // beams per utterance (> 1: beam search, rows R = B·nb; the running beams in bm)
-  BeamArgs bm;
-  bool forest = false;   // per-utterance lists installed (wcb_decode_bias_batch): every step takes bias = NULL
-  ForestDev fd;
-  bool logprobs = false; // wcb_decode_enable_logprobs: every step also writes its column of the context's lpbuf
-  bool sampling = false; // wcb_decode_enable_sampling: every step draws its tokens (the context's samp words)
-};
 
-// step-wise beam search: the beam path of wcb_generate one step per call (begin: cross-K/V of the
-// given encoder output, beam state, causal prefill of the per-clip prefix on every beam row)
-static void decode_begin_beams(wcb_handle* h, const void* enc, int B, int nb, const int32_t* prefix, int prefix_len,
-                               int max_new_tokens, float bias_boost, int min_new_tokens, wcb_state** out, void* stream) {
+// begin (greedy, nb = 1, or the beam path of wcb_generate, nb >= 2): the given encoder output into the context,
+// the per-clip prefix prefilled on every row of the clip, the first step's input ready; the length cap is
+// prefix + max_new_tokens, at most max_target_positions (generate()'s)
+static void decode_begin(wcb_handle* h, const void* enc, int B, int nb, const int32_t* prefix, int prefix_len,
+                         int max_new_tokens, float bias_boost, int min_new_tokens, wcb_state** out, void* stream) {
   REQUIRE(h && enc && out && B > 0 && B <= 64, "bad argument (1 <= B <= 64, enc and out required)");
   if (!h->ready) throw WcbError(WCB_ERR_STATE, "weights not finalized");
-  REQUIRE(nb >= 2 && nb <= kMaxBeams, "num_beams must be in [2, 8] (greedy: num_beams = 1)");
-  if (h->rules_on)
+  if (nb < 1) throw WcbError(WCB_ERR_ARG, "num_beams must be >= 1");
+  REQUIRE(nb <= kMaxBeams, "num_beams must be in [2, 8] (greedy: num_beams = 1)");
+  if (nb > 1 && h->rules_on)
     throw WcbError(WCB_ERR_UNSUPPORTED, "token rules are greedy only (num_beams = 1; wcb_set_token_rules(h, NULL) removes them)");
   const int R = B * nb;
   REQUIRE(R <= 64 * DecCtx::kMaxSub, "batch x num_beams > 512 rows: split the batch");
   REQUIRE(h->nctx < wcb_handle::kMaxCtx, "step-wise decoding needs a free decode context (decode_contexts <= 3)");
   REQUIRE(!h->step_state, "a step-wise decode is already active on this handle (wcb_decode_end first)");
-  REQUIRE(bias_boost >= 0.f && min_new_tokens >= 0 && max_new_tokens >= 1,
-          "bias_boost and min_new_tokens must be >= 0, max_new_tokens >= 1");
-  REQUIRE(bias_boost == 0.f || h->d.vocab <= kBeamMaxVocab, "beam search boost: vocabulary too large");
+  REQUIRE(bias_boost >= 0.f && min_new_tokens >= 0 && (nb == 1 || max_new_tokens >= 1),
+          nb == 1 ? "bias_boost and min_new_tokens must be >= 0" : "bias_boost and min_new_tokens must be >= 0, max_new_tokens >= 1");
+  REQUIRE(nb == 1 || bias_boost == 0.f || h->d.vocab <= kBeamMaxVocab, "beam search boost: vocabulary too large");
   const int P = prefix ? prefix_len : 1;
   REQUIRE(P >= 1 && P < h->d.n_text_ctx, "prefix_len must be in [1, max_target_positions)");
-  // generate(): the length cap is prefix + max_length, at most max_target_positions
-  const int Lt = std::min(P + max_new_tokens, h->d.n_text_ctx), max_new = Lt - P, Tc = Lt;
-  REQUIRE(Tc <= kBeamMaxLen, "beam search: more than 448 positions");
-  const int ci = wcb_handle::kMaxCtx - 1;
-  const int xm = h->beam_xmode;
-  ensure_dec_ws(h, B, R, Tc, max_new, xm, P > 1 ? R * std::min(prefill_chunk(R), P - 1) : R, ci, ci + 1);
-  DecCtx& D = h->dc[ci];
-  ensure_beam_buf(h, D, B, nb, max_new, Tc);
-  sync_in(h, stream, D.hs);
-  if (xm == 1) {
-    fill_xenc(h, ci, enc, B, D.hs);
-  } else {
-    sync_in(h, stream, h->he);
-    cross_kv(h, B, ci, enc);                        // on the encoder stream
-    HIPCHK(hipStreamSynchronize(h->he));
-  }
-  int* ints = D.ints.as<int>();
-  HIPCHK(hipMemsetAsync(ints, 0, (size_t)(I_NEXT + 4 * R) * 4, D.hs));
-  if (prefix) {   // per-clip prefixes [B][P] (host) on every beam row of the clip: [R][P]
-    std::vector<int32_t> rows((size_t)R * P);
-    for (int r = 0; r < R; ++r) std::copy(prefix + (size_t)(r / nb) * P, prefix + (size_t)(r / nb + 1) * P, rows.begin() + (size_t)r * P);
-    if (rows.size() * 4 > D.forced.bytes) { quiesce(h); D.forced.ensure(rows.size() * 4); }
-    HIPCHK(hipMemcpyAsync(D.forced.p, rows.data(), rows.size() * 4, hipMemcpyHostToDevice, D.hs));
-    HIPCHK(hipStreamSynchronize(D.hs));   // pageable host source
-  } else {
-    fill_i32(ints + I_NEXT, h->d.decoder_start_token_id, R, D.hs);
-  }
+  const int Tc = std::min(P + max_new_tokens, h->d.n_text_ctx);
+  REQUIRE(nb == 1 || Tc <= kBeamMaxLen, "beam search: more than 448 positions");
   // owned until the device work below succeeded (HIPCHK throws through here)
   std::unique_ptr<wcb_state> st(new wcb_state);
-  st->h = h; st->B = B; st->P = P; st->T = Tc; st->max_new = max_new; st->min_new = min_new_tokens;
-  st->xmode = xm; st->lam = bias_boost; st->nb = nb;
-  st->bm = beam_args(h, D, B, nb, P, Lt, Tc, max_new, min_new_tokens, bias_boost, h->empty_bias.get());
-  beam_init(st->bm, D.hs);   // before the prefill: the self-attention reads keys through the key map
-  StepCfg sc{R, Tc, max_new, ci, false, false, D.logits.as<float>(), (long)h->vocab_pad, h->empty_bias.get(),
-             bias_boost, min_new_tokens, D.forced.as<int>(), P};
-  sc.clips = B;
-  sc.nb = nb;
-  sc.xmode = xm;
-  sc.phys = st->bm.phys;
-  for (int p0 = 0, np; p0 + 1 < P; p0 += np) {
-    np = std::min(prefill_chunk(R), P - 1 - p0);
-    prefill_step(h, sc, np, D.forced.as<int>(), P);
-  }
-  if (prefix) gather_col(ints + I_NEXT, D.forced.as<int>(), R, P, P - 1, D.hs);
+  st->h = h; st->B = B; st->P = P; st->T = Tc; st->max_new = Tc - P; st->min_new = min_new_tokens;
+  st->xmode = nb > 1 ? h->beam_xmode : h->xmode; st->lam = bias_boost; st->nb = nb;
+  const int ci = wcb_handle::kMaxCtx - 1;
+  ensure_dec_ws(h, B, R, Tc, st->max_new, st->xmode, prefill_rows(R, P - 1), ci, ci + 1);
+  DecCtx& D = h->dc[ci];
+  if (nb > 1) ensure_beam_buf(h, D, B, nb, st->max_new, Tc);
+  sync_in(h, stream, D.hs);
+  // the caller's encoder output [B][1500][d] (model dtype) is copied / projected into owned buffers
+  enc_to_ctx(h, ci, enc, B, st->xmode, D.hs, stream);
+  const StepCfg sc = decode_start(h, ci, *st, prefix, /*shared=*/false, h->empty_bias.get());
+  decode_prompt(h, sc, P, prefix != nullptr);
   HIPCHK(hipStreamSynchronize(D.hs));
   h->step_state = st.release();
   *out = h->step_state;
@@ -2361,72 +2428,20 @@ static void decode_begin_beams(wcb_handle* h, const void* enc, int B, int nb, co
 
 int wcb_decode_begin(wcb_handle* h, const void* enc, int B, int num_beams, const int32_t* prefix, int prefix_len,
                      float bias_boost, int min_new_tokens, wcb_state** out, void* stream) {
-  return guarded(h, [&] {
-    REQUIRE(h && enc && out && B > 0 && B <= 64, "bad argument (1 <= B <= 64, enc and out required)");
-    if (!h->ready) throw WcbError(WCB_ERR_STATE, "weights not finalized");
-    if (num_beams != 1) {   // beam search to the default length cap (generate()'s max_length 448)
-      if (num_beams < 1) throw WcbError(WCB_ERR_ARG, "num_beams must be >= 1");
-      return decode_begin_beams(h, enc, B, num_beams, prefix, prefix_len, h->d.n_text_ctx, bias_boost, min_new_tokens, out,
-                                stream);
-    }
-    REQUIRE(h->nctx < wcb_handle::kMaxCtx, "step-wise decoding needs a free decode context (decode_contexts <= 3)");
-    REQUIRE(!h->step_state, "a step-wise decode is already active on this handle (wcb_decode_end first)");
-    REQUIRE(bias_boost >= 0.f && min_new_tokens >= 0, "bias_boost and min_new_tokens must be >= 0");
-    const int P = prefix ? prefix_len : 1;
-    REQUIRE(P >= 1 && P < h->d.n_text_ctx, "prefix_len must be in [1, max_target_positions)");
-    const int ci = wcb_handle::kMaxCtx - 1;
-    const int T = h->d.n_text_ctx, max_new = h->d.n_text_ctx - P;
-    const int xm = h->xmode;
-    ensure_dec_ws(h, B, B, T, max_new, xm, P > 1 ? B * std::min(prefill_chunk(B), P - 1) : B, ci, ci + 1);
-    DecCtx& D = h->dc[ci];
-    sync_in(h, stream, D.hs);
-    // the caller's encoder output [B][1500][d] (model dtype) is copied / projected into owned buffers
-    if (xm == 1) {
-      fill_xenc(h, ci, enc, B, D.hs);
-    } else {
-      sync_in(h, stream, h->he);
-      cross_kv(h, B, ci, enc);                        // on the encoder stream
-      HIPCHK(hipStreamSynchronize(h->he));
-    }
-    int* ints = D.ints.as<int>();
-    HIPCHK(hipMemsetAsync(ints, 0, (size_t)(I_NEXT + 6 * B) * 4, D.hs));   // (the rule state with finished[])
-    if (prefix) {   // per-row prefixes [B][P] (host), positions 0 .. P-2 prefilled, P-1 is the first input
-      if ((size_t)B * P * 4 > D.forced.bytes) { quiesce(h); D.forced.ensure((size_t)B * P * 4); }
-      HIPCHK(hipMemcpyAsync(D.forced.p, prefix, (size_t)B * P * 4, hipMemcpyHostToDevice, D.hs));
-      HIPCHK(hipStreamSynchronize(D.hs));   // pageable host source
-    } else {
-      fill_i32(ints + I_NEXT, h->d.decoder_start_token_id, B, D.hs);
-    }
-    StepCfg sc{B, T, max_new, ci, false, false, D.logits.as<float>(), (long)h->vocab_pad, h->empty_bias.get(),
-               bias_boost, min_new_tokens, D.forced.as<int>(), P};
-    sc.clips = B;
-    sc.xmode = xm;
-    for (int p0 = 0, np; p0 + 1 < P; p0 += np) {
-      np = std::min(prefill_chunk(B), P - 1 - p0);
-      prefill_step(h, sc, np, D.forced.as<int>(), P);
-    }
-    if (prefix) gather_col(ints + I_NEXT, D.forced.as<int>(), B, P, P - 1, D.hs);
-    step_embed(h, sc);   // the first step's input (every step's finalize embeds the next one)
-    HIPCHK(hipStreamSynchronize(D.hs));
-    auto* st = new wcb_state;
-    st->h = h; st->B = B; st->P = P; st->T = T; st->max_new = max_new; st->min_new = min_new_tokens;
-    st->xmode = xm; st->lam = bias_boost;
-    h->step_state = st;
-    *out = st;
-    sync_out(h, stream, D.hs);
+  return guarded(h, [&] {   // to the default length cap (generate()'s max_length 448)
+    decode_begin(h, enc, B, num_beams, prefix, prefix_len, h ? h->d.n_text_ctx : 0, bias_boost, min_new_tokens, out, stream);
   });
 }
 
 int wcb_decode_step(wcb_handle* h, wcb_state* st, const wcb_bias* bias, int32_t* next_ids, float* scores, void* stream) {
   return guarded(h, [&] {
-    REQUIRE(h && st && st->h == h && h->step_state == st && next_ids, "bad argument (state of this handle, next_ids)");
+    DecCtx& D = step_ctx(h, st, next_ids, "bad argument (state of this handle, next_ids)");
     REQUIRE(st->fwd == 0, "wcb_decode_step on a forward cache (wcb_forward_cached state)");
     if (st->steps >= st->max_new) {
       // the length cap: refused, except for a finished beam search, whose steps are frozen (identity
       // parents, pad ids; the device position stopped at the last cache slot)
       bool frozen = false;
       if (st->nb > 1) {
-        DecCtx& D = h->dc[wcb_handle::kMaxCtx - 1];
         int v = 0;
         HIPCHK(hipMemcpyAsync(&v, D.ints.as<int>() + I_DONE, 4, hipMemcpyDeviceToHost, D.hs));
         HIPCHK(hipStreamSynchronize(D.hs));
@@ -2439,18 +2454,17 @@ int wcb_decode_step(wcb_handle* h, wcb_state* st, const wcb_bias* bias, int32_t*
     REQUIRE(bs == h->empty_bias.get() || bs->owner == h, "bias automaton was created on another handle");
     REQUIRE(bs->vocab == h->d.vocab, "bias automaton built for another vocabulary");
     REQUIRE(st->steps == 0 || bs->id == st->bias_id, "the bias automaton must stay the same for the whole decode");
-    const int ci = wcb_handle::kMaxCtx - 1;
-    DecCtx& D = h->dc[ci];
     sync_in(h, stream, D.hs);
     const int R = st->B * st->nb;
-    StepCfg sc{R, st->T, st->max_new, ci, true, true, D.logits.as<float>(), (long)h->vocab_pad, bs, st->lam,
-               st->min_new, D.forced.as<int>(), 0};
+    StepCfg sc = step_cfg(h, wcb_handle::kMaxCtx - 1, R, st->T, st->max_new);
+    sc.lm_head = true;
+    sc.select = true;
+    sc.bias = bs; sc.lam = st->lam; sc.min_new = st->min_new;
     sc.clips = st->B;
     sc.xmode = st->xmode;
     sc.host_pos = st->P - 1 + st->steps;
     if (st->nb > 1) {   // beam step: the running beams' new tokens, their scores (running log-prob sums)
-      beam_set_bias(st->bm, bs);
-      if (st->forest) beam_set_forest(st->bm, st->fd);
+      set_automaton(st->bm, bs, st->forest ? &st->fd : nullptr);
       sc.nb = st->nb;
       sc.phys = st->bm.phys;
       sc.beam = &st->bm;
@@ -2463,7 +2477,7 @@ int wcb_decode_step(wcb_handle* h, wcb_state* st, const wcb_bias* bias, int32_t*
     }
     if (st->forest) sc.forest = &st->fd;
     decode_step(h, sc);
-    HIPCHK(hipMemcpyAsync(next_ids, D.ints.as<int>() + I_NEXT, (size_t)R * 4, hipMemcpyDeviceToDevice, D.hs));
+    HIPCHK(hipMemcpyAsync(next_ids, RowInts(D, R).next, (size_t)R * 4, hipMemcpyDeviceToDevice, D.hs));
     if (st->nb > 1 && scores)
       HIPCHK(hipMemcpyAsync(scores, st->bm.run_sc, (size_t)R * 4, hipMemcpyDeviceToDevice, D.hs));
     st->bias_id = bs->id;
@@ -2474,17 +2488,12 @@ int wcb_decode_step(wcb_handle* h, wcb_state* st, const wcb_bias* bias, int32_t*
 
 int wcb_decode_bias_batch(wcb_handle* h, wcb_state* st, const wcb_bias_batch* bb) {
   return guarded(h, [&] {
-    REQUIRE(h && st && st->h == h && h->step_state == st && bb, "bad argument (state of this handle, bias batch)");
+    DecCtx& D = step_ctx(h, st, bb, "bad argument (state of this handle, bias batch)");
     REQUIRE(st->fwd == 0, "wcb_decode_bias_batch on a forward cache (wcb_forward_cached state)");
     REQUIRE(st->steps == 0, "wcb_decode_bias_batch: after the first step (install it right after wcb_decode_begin)");
     REQUIRE(bb->vocab == h->d.vocab, "bias batch built for another vocabulary");
     REQUIRE(bb->B == st->B, "bias batch: built for " + std::to_string(bb->B) + " clips, the state has " + std::to_string(st->B));
-    DecCtx& D = h->dc[wcb_handle::kMaxCtx - 1];
-    const int R = st->B * st->nb;
-    int* ints = D.ints.as<int>();
-    st->fd = install_forest(h, D, bb);
-    forest_init(st->fd.f, ints + I_NEXT + R, st->nb == 1 ? ints + I_NEXT + 3 * R : nullptr, R, st->nb, D.hs);
-    st->forest = true;
+    start_forest(h, D, *st, bb);
   });
 }
 
@@ -2492,16 +2501,15 @@ int wcb_decode_begin_beams(wcb_handle* h, const void* enc, int B, int num_beams,
                            int max_new_tokens, float bias_boost, int min_new_tokens, wcb_state** out, void* stream) {
   return guarded(h, [&] {
     REQUIRE(num_beams >= 2, "wcb_decode_begin_beams: num_beams must be >= 2 (greedy: wcb_decode_begin)");
-    decode_begin_beams(h, enc, B, num_beams, prefix, prefix_len, max_new_tokens, bias_boost, min_new_tokens, out, stream);
+    decode_begin(h, enc, B, num_beams, prefix, prefix_len, max_new_tokens, bias_boost, min_new_tokens, out, stream);
   });
 }
 
 int wcb_decode_parents(wcb_handle* h, wcb_state* st, int32_t* parents, void* stream) {
   return guarded(h, [&] {
-    REQUIRE(h && st && st->h == h && h->step_state == st && parents, "bad argument (state of this handle, parents)");
+    DecCtx& D = step_ctx(h, st, parents, "bad argument (state of this handle, parents)");
     REQUIRE(st->nb > 1, "wcb_decode_parents: not a beam-search state");
     REQUIRE(st->steps > 0, "wcb_decode_parents: no step taken yet");
-    DecCtx& D = h->dc[wcb_handle::kMaxCtx - 1];
     sync_in(h, stream, D.hs);
     HIPCHK(hipMemcpyAsync(parents, st->bm.parent, (size_t)st->B * st->nb * 4, hipMemcpyDeviceToDevice, D.hs));
     sync_out(h, stream, D.hs);
@@ -2510,11 +2518,10 @@ int wcb_decode_parents(wcb_handle* h, wcb_state* st, int32_t* parents, void* str
 
 int wcb_decode_info(wcb_handle* h, wcb_state* st, int32_t* max_new, int32_t* steps, int32_t* done) {
   return guarded(h, [&] {
-    REQUIRE(h && st && st->h == h && h->step_state == st, "bad argument (state of this handle)");
+    DecCtx& D = step_ctx(h, st);
     if (max_new) *max_new = st->max_new;
     if (steps) *steps = st->steps;
     if (done) {   // the device's all-finished flag (I_DONE: the step at which every utterance / row was done)
-      DecCtx& D = h->dc[wcb_handle::kMaxCtx - 1];
       int v = 0;
       HIPCHK(hipMemcpyAsync(&v, D.ints.as<int>() + I_DONE, 4, hipMemcpyDeviceToHost, D.hs));
       HIPCHK(hipStreamSynchronize(D.hs));
@@ -2525,9 +2532,8 @@ int wcb_decode_info(wcb_handle* h, wcb_state* st, int32_t* max_new, int32_t* ste
 
 int wcb_decode_result(wcb_handle* h, wcb_state* st, int32_t* out_ids, int out_ld, int32_t* out_steps, void* stream) {
   return guarded(h, [&] {
-    REQUIRE(h && st && st->h == h && h->step_state == st && out_ids && out_steps, "bad argument");
+    DecCtx& D = step_ctx(h, st, out_ids && out_steps, "bad argument");
     REQUIRE(st->fwd == 0, "wcb_decode_result on a forward cache (wcb_forward_cached state)");
-    DecCtx& D = h->dc[wcb_handle::kMaxCtx - 1];
     int* ints = D.ints.as<int>();
     sync_in(h, stream, D.hs);
     int n = st->steps;
@@ -2552,11 +2558,10 @@ int wcb_decode_result(wcb_handle* h, wcb_state* st, int32_t* out_ids, int out_ld
 
 int wcb_decode_enable_logprobs(wcb_handle* h, wcb_state* st) {
   return guarded(h, [&] {
-    REQUIRE(h && st && st->h == h && h->step_state == st, "bad argument (state of this handle)");
+    DecCtx& D = step_ctx(h, st);
     if (st->nb > 1) throw WcbError(WCB_ERR_UNSUPPORTED, "token log-probs are greedy only (a beam-search state)");
     if (st->fwd != 0) throw WcbError(WCB_ERR_STATE, "wcb_decode_enable_logprobs on a forward cache (wcb_forward_cached state)");
     if (st->steps != 0) throw WcbError(WCB_ERR_STATE, "wcb_decode_enable_logprobs: after the first step (right after wcb_decode_begin)");
-    DecCtx& D = h->dc[wcb_handle::kMaxCtx - 1];
     ensure_lp_ws(h, D, st->B, st->max_new);
     HIPCHK(hipMemsetAsync(D.lpbuf.p, 0, (size_t)st->B * st->max_new * 4, D.hs));
     st->logprobs = true;
@@ -2565,26 +2570,25 @@ int wcb_decode_enable_logprobs(wcb_handle* h, wcb_state* st) {
 
 int wcb_decode_enable_sampling(wcb_handle* h, wcb_state* st, float temperature, const uint64_t* seeds) {
   return guarded(h, [&] {
-    REQUIRE(h && st && st->h == h && h->step_state == st, "bad argument (state of this handle)");
+    DecCtx& D = step_ctx(h, st);
     check_sampling(temperature, seeds);
     if (st->nb > 1) throw WcbError(WCB_ERR_UNSUPPORTED, "sampling is greedy only (a beam-search state)");
     if (h->rules_on && h->rules_ts.on)
       throw WcbError(WCB_ERR_UNSUPPORTED, "timestamp decoding with sampling is not supported (greedy only)");
     if (st->fwd != 0) throw WcbError(WCB_ERR_STATE, "wcb_decode_enable_sampling on a forward cache (wcb_forward_cached state)");
     if (st->steps != 0) throw WcbError(WCB_ERR_STATE, "wcb_decode_enable_sampling: after the first step (right after wcb_decode_begin)");
-    install_sampling(h->dc[wcb_handle::kMaxCtx - 1], temperature, seeds, st->B);
+    install_sampling(D, temperature, seeds, st->B);
     st->sampling = true;
   });
 }
 
 int wcb_decode_logprobs(wcb_handle* h, wcb_state* st, float* out, int out_ld, int32_t* out_steps, void* stream) {
   return guarded(h, [&] {
-    REQUIRE(h && st && st->h == h && h->step_state == st && out && out_steps, "bad argument");
+    DecCtx& D = step_ctx(h, st, out && out_steps, "bad argument");
     if (!st->logprobs) throw WcbError(WCB_ERR_STATE, "wcb_decode_logprobs: log-probs are off (wcb_decode_enable_logprobs)");
     const int n = st->steps;
     REQUIRE(out_ld >= n && out_ld >= 1, "wcb_decode_logprobs: out_ld " + std::to_string(out_ld) + " < the " +
                                             std::to_string(n) + " steps taken");
-    DecCtx& D = h->dc[wcb_handle::kMaxCtx - 1];
     sync_in(h, stream, D.hs);
     if (n > 0)
       HIPCHK(hipMemcpy2DAsync(out, (size_t)out_ld * 4, D.lpbuf.p, (size_t)st->max_new * 4, (size_t)n * 4, st->B,
@@ -2596,8 +2600,7 @@ int wcb_decode_logprobs(wcb_handle* h, wcb_state* st, float* out, int out_ld, in
 
 int wcb_decode_end(wcb_handle* h, wcb_state* st) {
   return guarded(h, [&] {
-    REQUIRE(h && st && st->h == h && h->step_state == st, "bad argument (state of this handle)");
-    HIPCHK(hipStreamSynchronize(h->dc[wcb_handle::kMaxCtx - 1].hs));
+    HIPCHK(hipStreamSynchronize(step_ctx(h, st).hs));
     check_dev_err(h);
     h->step_state = nullptr;
     delete st;
@@ -2613,67 +2616,49 @@ int wcb_synchronize(wcb_handle* h) {
   });
 }
 
-// teacher forcing on decode context `buf` once its encoder-side buffer is ready (ev_xkv[buf] recorded
-// on the encoder stream): causal prefill of positions 0 .. T-1 of every row, logits of every position
-static void forward_decode(wcb_handle* h, int buf, int B, const int32_t* dec_ids, int T, float* logits) {
+// Teacher forcing: the encoder output of `mel` (wcb_forward; also into enc_out when given) or the given one in its
+// place (wcb_forward_enc: the same buffer or the same cross-K/V GEMM over it, so the logits are equal bit for bit)
+// into the next decode context, then a causal prefill of positions 0 .. T-1 of every row, logits of every position
+static void forward_impl(wcb_handle* h, const float* mel, const void* enc, void* enc_out, int B, const int32_t* dec_ids,
+                         int T, float* logits, void* stream) {
+  REQUIRE(h && (mel || enc) && dec_ids && logits && B > 0 && T > 0, "bad argument");
+  if (!h->ready) throw WcbError(WCB_ERR_STATE, "weights not finalized");
+  REQUIRE(B <= 64, "batch > 64 per handle");
+  REQUIRE(T <= h->d.n_text_ctx, "decoder_input_ids longer than max_target_positions");
+  if (mel) ensure_enc_ws(h, B);
+  ensure_dec_ws(h, B, B, T, 1, h->xmode, prefill_rows(B, T));
+  const int buf = h->gen_count++ % h->nctx;
   DecCtx& D = h->dc[buf];
-  HIPCHK(hipStreamWaitEvent(D.hs, h->ev_xkv[buf], 0));
-  int* ints = D.ints.as<int>();
-  HIPCHK(hipMemsetAsync(ints, 0, (size_t)(I_NEXT + 4 * B) * 4, D.hs));
-  for (int p0 = 0, np; p0 < T; p0 += np) {
-    np = std::min(prefill_chunk(B), T - p0);
-    StepCfg sc{B, T, 1, buf, true, false, logits + (size_t)p0 * h->d.vocab, (long)T * h->d.vocab, nullptr, 0.f,
-               0, nullptr, 0};
-    sc.xmode = h->xmode;
-    prefill_step(h, sc, np, dec_ids, T);
+  sync_in(h, stream, h->he);
+  HIPCHK(hipStreamWaitEvent(h->he, h->ev_dec[buf], 0));
+  if (mel) {
+    enc_out = enc_out ? enc_out : h->encout.p;
+    encode_impl(h, mel, B, enc_out);
+    enc = enc_out;
   }
+  enc_to_ctx(h, buf, enc, B, h->xmode, h->he, stream);
+  HIPCHK(hipStreamWaitEvent(D.hs, h->ev_xkv[buf], 0));
+  HIPCHK(hipMemsetAsync(D.ints.p, 0, RowInts::words(B) * 4, D.hs));
+  StepCfg sc = step_cfg(h, buf, B, T, 1);
+  sc.lm_head = true;
+  sc.logits_ld = (long)T * h->d.vocab;   // the caller's [B][T][V]: a pass writes positions p0 .. of every row
+  prefill_range(h, sc, dec_ids, T, 0, T, [&](StepCfg& c, int p0, int) { c.logits_out = logits + (size_t)p0 * h->d.vocab; });
   HIPCHK(hipEventRecord(h->ev_dec[buf], D.hs));
+  sync_out(h, stream, D.hs);
 }
 
 int wcb_forward(wcb_handle* h, const float* mel, int B, const int32_t* dec_ids, int T, float* logits, void* enc_out,
                 void* stream) {
   return guarded(h, [&] {
-    REQUIRE(h && mel && dec_ids && logits && B > 0 && T > 0, "bad argument");
-    if (!h->ready) throw WcbError(WCB_ERR_STATE, "weights not finalized");
-    REQUIRE(B <= 64, "batch > 64 per handle");
-    REQUIRE(T <= h->d.n_text_ctx, "decoder_input_ids longer than max_target_positions");
-    ensure_enc_ws(h, B);
-    ensure_dec_ws(h, B, B, T, 1, h->xmode, B * std::min(prefill_chunk(B), T));
-    const int buf = h->gen_count++ % h->nctx;
-    sync_in(h, stream, h->he);
-    HIPCHK(hipStreamWaitEvent(h->he, h->ev_dec[buf], 0));
-    if (h->xmode == 1) {
-      void* eo = enc_out ? enc_out : h->encout.p;
-      encode_impl(h, mel, B, eo);
-      fill_xenc(h, buf, eo, B, h->he);
-    } else {
-      void* eo = enc_out ? enc_out : h->encout.p;
-      encode_impl(h, mel, B, eo);
-      cross_kv(h, B, buf, eo);
-    }
-    HIPCHK(hipEventRecord(h->ev_xkv[buf], h->he));
-    forward_decode(h, buf, B, dec_ids, T, logits);
-    sync_out(h, stream, h->dc[buf].hs);
+    REQUIRE(mel, "bad argument");
+    forward_impl(h, mel, nullptr, enc_out, B, dec_ids, T, logits, stream);
   });
 }
 
 int wcb_forward_enc(wcb_handle* h, const void* enc, int B, const int32_t* dec_ids, int T, float* logits, void* stream) {
   return guarded(h, [&] {
-    REQUIRE(h && enc && dec_ids && logits && B > 0 && T > 0, "bad argument");
-    if (!h->ready) throw WcbError(WCB_ERR_STATE, "weights not finalized");
-    REQUIRE(B <= 64, "batch > 64 per handle");
-    REQUIRE(T <= h->d.n_text_ctx, "decoder_input_ids longer than max_target_positions");
-    ensure_dec_ws(h, B, B, T, 1, h->xmode, B * std::min(prefill_chunk(B), T));
-    const int buf = h->gen_count++ % h->nctx;
-    sync_in(h, stream, h->he);
-    HIPCHK(hipStreamWaitEvent(h->he, h->ev_dec[buf], 0));
-    // the given encoder output takes the place of encode_impl's: the same buffer (encoder space) or the
-    // same cross-K/V GEMM over it (K/V formulation), so the logits equal wcb_forward's bit for bit
-    if (h->xmode == 1) fill_xenc(h, buf, enc, B, h->he);
-    else cross_kv(h, B, buf, enc);
-    HIPCHK(hipEventRecord(h->ev_xkv[buf], h->he));
-    forward_decode(h, buf, B, dec_ids, T, logits);
-    sync_out(h, stream, h->dc[buf].hs);
+    REQUIRE(enc, "bad argument");
+    forward_impl(h, nullptr, enc, nullptr, B, dec_ids, T, logits, stream);
   });
 }
 
@@ -2721,7 +2706,7 @@ int wcb_align(wcb_handle* h, const void* enc, int B, const int32_t* ids, int ld,
         sb[b] = cfg->num_frames[b] / 2;
       }
     int buf, xm;
-    const int rows = B * std::min(prefill_chunk(B), T);
+    const int rows = prefill_rows(B, T);
     if (enc) {
       xm = h->xmode;
       ensure_dec_ws(h, B, B, T, 1, xm, rows);
@@ -2754,9 +2739,7 @@ int wcb_align(wcb_handle* h, const void* enc, int B, const int32_t* ids, int ld,
     if (enc) {   // the given encoder output into the context, as wcb_forward_enc
       sync_in(h, stream, h->he);
       HIPCHK(hipStreamWaitEvent(h->he, h->ev_dec[buf], 0));
-      if (xm == 1) fill_xenc(h, buf, enc, B, h->he);
-      else cross_kv(h, B, buf, enc);
-      HIPCHK(hipEventRecord(h->ev_xkv[buf], h->he));
+      enc_to_ctx(h, buf, enc, B, xm, h->he, stream);
       HIPCHK(hipStreamWaitEvent(D.hs, h->ev_xkv[buf], 0));
     }
     sync_in(h, stream, D.hs);   // the ids
@@ -2770,19 +2753,16 @@ int wcb_align(wcb_handle* h, const void* enc, int B, const int32_t* ids, int ld,
     align_prep(ids, ld, n, prefix ? h->al_prefix.as<int>() : nullptr, P, h->d.decoder_start_token_id, h->d.eos_token_id,
                h->d.vocab, B, tf, lens, D.hs);
     ap.P = P; ap.nrow = nrow; ap.w = h->al_w.as<float>();
-    int* ints = D.ints.as<int>();
+    StepCfg sc = step_cfg(h, buf, B, T, 1);
+    sc.xmode = xm;
     for (int c0 = 0; c0 < B && nrow > 0; c0 += gsz) {
       ap.clip0 = c0; ap.nclip = std::min(gsz, B - c0);
       // teacher forcing over prefix + ids, LM head off: the causal prefill of wcb_forward_enc
-      HIPCHK(hipMemsetAsync(ints, 0, (size_t)(I_NEXT + 4 * B) * 4, D.hs));
-      for (int p0 = 0, np; p0 < T; p0 += np) {
-        np = std::min(prefill_chunk(B), T - p0);
-        StepCfg sc{B, T, 1, buf, false, false, nullptr, 0, nullptr, 0.f, 0, nullptr, 0};
-        sc.xmode = xm;
+      HIPCHK(hipMemsetAsync(D.ints.p, 0, RowInts::words(B) * 4, D.hs));
+      prefill_range(h, sc, tf, T, 0, T, [&](StepCfg& c, int p0, int np) {
         ap.pos0 = p0;
-        sc.align = p0 + np > P ? &ap : nullptr;   // (a pass over prefix positions alone has no row to keep)
-        prefill_step(h, sc, np, tf, T);
-      }
+        c.align = p0 + np > P ? &ap : nullptr;   // (a pass over prefix positions alone has no row to keep)
+      });
       h->timed("align_matrix", 0, (double)ap.nclip * per_clip, D.hs, [&] {
         if (!align_matrix(ap.w, ap.nclip, ap.heads_total, nrow, S, lens + c0, frames + c0, cfg->median_width,
                           M + (size_t)c0 * nrow * S, D.hs))
@@ -2912,27 +2892,25 @@ int wcb_dtw_host(const float* M, int m, int S, long ld, int32_t* frames, int n_o
 
 int wcb_forward_cached(wcb_handle* h, wcb_state* st, const int32_t* dec_ids, int T, float* logits, void* stream) {
   return guarded(h, [&] {
-    REQUIRE(h && st && st->h == h && h->step_state == st && dec_ids && logits && T > 0,
-            "bad argument (state of this handle, dec_ids, logits, T > 0)");
+    step_ctx(h, st, dec_ids && logits && T > 0, "bad argument (state of this handle, dec_ids, logits, T > 0)");
     REQUIRE(st->steps == 0, "wcb_forward_cached on a state that wcb_decode_step has advanced");
     REQUIRE(st->P == 1, "wcb_forward_cached needs a state begun without a prefix");
     REQUIRE(st->fwd + T <= st->T, "past_key_values + decoder_input_ids exceed max_target_positions");
     const int ci = wcb_handle::kMaxCtx - 1, B = st->B;
-    ensure_dec_ws(h, B, B, st->T, st->max_new, st->xmode, B * std::min(prefill_chunk(B), T), ci, ci + 1);
+    ensure_dec_ws(h, B, B, st->T, st->max_new, st->xmode, prefill_rows(B, T), ci, ci + 1);
     DecCtx& D = h->dc[ci];
     sync_in(h, stream, D.hs);
     // the new ids at their absolute positions of the [B][T] forced buffer (prefill_ids reads src[b·T + pos])
     if ((size_t)B * st->T * 4 > D.forced.bytes) { quiesce(h); D.forced.ensure((size_t)B * st->T * 4); }
     HIPCHK(hipMemcpy2DAsync(D.forced.as<int>() + st->fwd, (size_t)st->T * 4, dec_ids, (size_t)T * 4, (size_t)T * 4, B,
                             hipMemcpyDeviceToDevice, D.hs));
-    for (int p0 = 0, np; p0 < T; p0 += np) {
-      np = std::min(prefill_chunk(B), T - p0);
-      StepCfg sc{B, st->T, 1, ci, true, false, logits + (size_t)p0 * h->d.vocab, (long)T * h->d.vocab, nullptr, 0.f,
-                 0, nullptr, 0};
-      sc.clips = B;
-      sc.xmode = st->xmode;
-      prefill_step(h, sc, np, D.forced.as<int>(), st->T);
-    }
+    StepCfg sc = step_cfg(h, ci, B, st->T, 1);
+    sc.lm_head = true;
+    sc.logits_ld = (long)T * h->d.vocab;   // the caller's [B][T][V], as wcb_forward
+    sc.clips = B;
+    sc.xmode = st->xmode;
+    prefill_range(h, sc, D.forced.as<int>(), st->T, 0, T,
+                  [&](StepCfg& c, int p0, int) { c.logits_out = logits + (size_t)p0 * h->d.vocab; });
     st->fwd += T;
     sync_out(h, stream, D.hs);
   });
@@ -3070,8 +3048,10 @@ void wcb_bias_destroy(wcb_bias* b) {
       quiesce(h);
     } catch (...) {
     }
+    const std::string id = "/" + std::to_string(b->id) + "/";
     for (DecCtx& D : h->dc)
-      if (D.all_gkeys().find("/" + std::to_string(b->id) + "/") != std::string::npos) D.drop_graphs();
+      for (const StepGraphs& g : D.graphs)
+        if (g.key.find(id) != std::string::npos) { D.drop_graphs(); break; }
     h->biases.erase(std::remove(h->biases.begin(), h->biases.end(), b), h->biases.end());
   }
   for (DevBuf* x : {&b->root_bits, &b->root_child, &b->trans_off, &b->trans_tok, &b->trans_dst, &b->st_depth, &b->st_keep})

@@ -750,7 +750,6 @@ class WhisperCB:
         if not 1 <= num_beams <= 8:
             raise ValueError("num_beams must be in [1, 8]")
         x = x_all
-        B = x.shape[0]
         prefix = [self.dims.decoder_start_token_id]
         if prompt_ids is not None:
             prefix = [int(t) for t in prompt_ids] + prefix
@@ -768,82 +767,56 @@ class WhisperCB:
         else:
             bl = self.bias_list(phrases) if (phrases and bias_boost > 0) else None
         cfg = _lib.WcbGenCfg(max_new, int(min_new_tokens), num_beams, float(bias_boost), int(use_graph), int(not block))
-        out = torch.empty(B, max_new, dtype=torch.int32, device=self.device)
-        steps = C.c_int32(0)
-        pre = np.asarray(prefix, dtype=np.int32)
         smp = _lib.WcbSampleCfg(T, seeds.ctypes.data_as(C.POINTER(C.c_uint64))) if seeds is not None else None
         self._install_rules(rules)
-        if output_logprobs:
-            res = self._generate_scored(x, cfg, bl, bias_lists if bias_boost > 0 else None, prefix, pre, out, block, smp)
-            if return_timestamps:
-                res.segments = self._segments(res.sequences[:, len(prefix):].cpu().numpy())
-            return res
-        if smp is not None:
-            bb = BiasBatch(self, bias_lists) if (bias_lists is not None and bias_boost > 0) else None
-            try:
-                _lib.check(self._lib.wcb_generate_sampled(self._h, _ptr(x), B, C.byref(cfg), C.byref(smp),
-                                                          bl._h if (bl and not bb) else None, bb._h if bb else None,
-                                                          pre.ctypes.data if len(prefix) > 1 else None, len(prefix),
-                                                          _ptr(out), None, C.byref(steps), _stream(self.device)),
-                           self._h, "wcb_generate_sampled")
-            finally:
-                if bb:
-                    bb.close()   # the call copied it, as it copied the seeds (also with block=False)
-        elif bias_lists is not None and bias_boost > 0:
-            bb = BiasBatch(self, bias_lists)   # per call: not in the automaton LRU
-            try:
-                _lib.check(self._lib.wcb_generate_biased(self._h, _ptr(x), B, C.byref(cfg), bb._h,
-                                                         pre.ctypes.data if len(prefix) > 1 else None, len(prefix),
-                                                         _ptr(out), C.byref(steps), _stream(self.device)),
-                           self._h, "wcb_generate_biased")
-            finally:
-                bb.close()   # the call copied it (also with block=False)
-        else:
-            _lib.check(self._lib.wcb_generate(self._h, _ptr(x), B, C.byref(cfg), bl._h if bl else None,
-                                              pre.ctypes.data if len(prefix) > 1 else None, len(prefix),
-                                              _ptr(out), C.byref(steps), _stream(self.device)),
-                       self._h, "wcb_generate")
-        if not block:
-            return out[:, :steps.value]            # int32, valid after synchronize()
-        ids = out[:, :steps.value].to(torch.int64)
-        if return_dict_in_generate:
-            sot = torch.tensor(prefix, dtype=torch.int64, device=self.device)[None].expand(B, -1)
-            return GenerateOutput(sequences=torch.cat([sot, ids], dim=1),
-                                  segments=self._segments(ids.cpu().numpy()) if return_timestamps else None)
-        return self._whisper_trim(ids)
+        out, n, lp, ss = self._decode_call(x, cfg, bl, bias_lists if bias_boost > 0 else None, prefix, smp, output_logprobs)
+        return self._generate_result(out, n, prefix, block, return_dict_in_generate, lp, ss, return_timestamps)
 
-    def _generate_scored(self, x, cfg, bl, bias_lists, prefix, pre, out, block, smp=None) -> GenerateOutput:
-        """generate(output_logprobs=True) on one library call: wcb_generate_scored (smp: wcb_generate_sampled)
-        with the shared automaton `bl`, the per-clip `bias_lists`, or neither."""
+    def _decode_call(self, x, cfg, bl, bias_lists, prefix, smp, scored):
+        """One library decode of the batch x: the shared automaton `bl`, the per-clip `bias_lists` (a BiasBatch that
+        lives for this call) or neither; `smp` samples; `scored` asks for token log-probs (greedy) or sequence scores
+        (beams). Returns (ids int32 [B, max_new], generated columns, log-probs or None, sequence scores or None)."""
         B, max_new, beams = x.shape[0], cfg.max_new_tokens, cfg.num_beams > 1
-        lp = None if beams else torch.zeros(B, max_new, dtype=torch.float32, device=self.device)
-        ss = torch.zeros(B, dtype=torch.float32, device=self.device) if beams else None
+        out = torch.empty(B, max_new, dtype=torch.int32, device=self.device)
+        lp = torch.zeros(B, max_new, dtype=torch.float32, device=self.device) if scored and not beams else None
+        ss = torch.zeros(B, dtype=torch.float32, device=self.device) if scored and beams else None
         steps = C.c_int32(0)
+        pre = np.asarray(prefix, dtype=np.int32)
         bb = BiasBatch(self, bias_lists) if bias_lists is not None else None   # per call: not in the automaton LRU
+        head = (self._h, _ptr(x), B, C.byref(cfg))
+        bias = (bl._h if (bl and not bb) else None, bb._h if bb else None)
+        mid = (pre.ctypes.data if len(prefix) > 1 else None, len(prefix), _ptr(out))
+        scores = (_ptr(lp) if lp is not None else None, _ptr(ss) if ss is not None else None)
+        tail = (C.byref(steps), _stream(self.device))
+        if smp is not None:
+            name, args = "wcb_generate_sampled", head + (C.byref(smp),) + bias + mid + scores[:1] + tail
+        elif scored:
+            name, args = "wcb_generate_scored", head + bias + mid + scores + tail
+        elif bb:
+            name, args = "wcb_generate_biased", head + bias[1:] + mid + tail
+        else:
+            name, args = "wcb_generate", head + bias[:1] + mid + tail
         try:
-            if smp is not None:
-                _lib.check(self._lib.wcb_generate_sampled(self._h, _ptr(x), B, C.byref(cfg), C.byref(smp),
-                                                          bl._h if (bl and not bb) else None, bb._h if bb else None,
-                                                          pre.ctypes.data if len(prefix) > 1 else None, len(prefix),
-                                                          _ptr(out), _ptr(lp), C.byref(steps), _stream(self.device)),
-                           self._h, "wcb_generate_sampled")
-            else:
-                _lib.check(self._lib.wcb_generate_scored(self._h, _ptr(x), B, C.byref(cfg),
-                                                         bl._h if (bl and not bb) else None, bb._h if bb else None,
-                                                         pre.ctypes.data if len(prefix) > 1 else None, len(prefix),
-                                                         _ptr(out), _ptr(lp) if lp is not None else None,
-                                                         _ptr(ss) if ss is not None else None, C.byref(steps),
-                                                         _stream(self.device)), self._h, "wcb_generate_scored")
+            _lib.check(getattr(self._lib, name)(*args), self._h, name)
         finally:
             if bb:
-                bb.close()   # the call copied it (also with block=False)
-        n = steps.value
-        if not block:   # device views, valid after synchronize()
+                bb.close()   # the call copied it, as it copied the seeds (also with block=False)
+        return out, steps.value, lp, ss
+
+    def _generate_result(self, out, n, prefix, block, as_dict, lp=None, ss=None, timestamps=False):
+        """generate()'s return value from a decode's ids [B, max_new] (n columns generated) and its scores, if any."""
+        if not block:   # device views (int32 ids), valid after synchronize()
+            if lp is None and ss is None:
+                return out[:, :n]
             return GenerateOutput(sequences=out[:, :n], token_logprobs=lp[:, :n] if lp is not None else None,
                                   sequences_scores=ss)
         ids = out[:, :n].to(torch.int64)
+        if not as_dict:
+            return self._whisper_trim(ids)
+        B = ids.shape[0]
         sot = torch.tensor(prefix, dtype=torch.int64, device=self.device)[None].expand(B, -1)
-        res = GenerateOutput(sequences=torch.cat([sot, ids], dim=1), sequences_scores=ss)
+        res = GenerateOutput(sequences=torch.cat([sot, ids], dim=1), sequences_scores=ss,
+                             segments=self._segments(ids.cpu().numpy()) if timestamps else None)
         if lp is not None:
             res.token_logprobs = lp[:, :n]
             # Whisper's avg_logprob on the host: each row's tokens up to and including its EOS (a finished row's
