@@ -333,6 +333,31 @@ int wcb_decode_enable_sampling(wcb_handle*, wcb_state*, float temperature, const
 int wcb_op_lm_head_sample(int dtype, const void* A, const void* W, int M, int V, int K, int walkers,
                           float temperature, const uint64_t* seeds, int step, float* logits, long ld,
                           float* lse, int32_t* sampled, void* stream);
+
+/* Per-clip prompts of different lengths in one greedy batch. Clip b's prompt of prompt_len[b] tokens
+ * — the decoder start token last, so 1 = no prompt — sits right-aligned in row b of `prompts` HOST [B][prompt_ld]:
+ * columns prompt_ld - prompt_len[b] .. prompt_ld - 1; the columns before it are ignored (the library writes the pad
+ * token there). Clip b decodes exactly as it decodes alone with that prompt as `prefix`: its position embeddings
+ * count from its own first token and its self-attention never reads the slots before it, while the step counter,
+ * the K/V write slot and the captured graph stay those of a prompt_ld-long dense prompt. Both arrays are copied on
+ * the decode stream through pinned staging: they are free on return, async_out = 1 included; the graph key holds
+ * the fact "ragged", never the lengths. All lengths equal to prompt_ld: the dense kernels.
+ * wcb_generate_prompted = wcb_generate_sampled (smp non-NULL) / wcb_generate_scored's greedy form (smp NULL;
+ * out_logprobs may be NULL) with these prompts; it composes with the shared automaton, the bias batch, log-probs,
+ * sampling and the handle's token rules. out_ids [B][cfg->max_new_tokens] as every wcb_generate*: the generated
+ * columns only. wcb_decode_begin_prompted = wcb_decode_begin's greedy form; wcb_decode_step / _result / _logprobs /
+ * _enable_logprobs / _enable_sampling / _bias_batch then work on the state as on any greedy one.
+ * Errors: prompt_len[b] outside [1, prompt_ld], prompt_ld + max_new_tokens > max_target_positions + 1 (the rule of
+ * prefix_len): WCB_ERR_ARG; num_beams > 1: WCB_ERR_UNSUPPORTED (beam scores are normalised by a length that counts
+ * the prompt, so a clip would not decode as it does alone). wcb_align (token timestamps) takes one shared prefix:
+ * not after a ragged call with enc = NULL. */
+int wcb_generate_prompted(wcb_handle*, const float* mel, int B, const wcb_gen_cfg*, const wcb_sample_cfg*,
+                          const wcb_bias*, const wcb_bias_batch*, const int32_t* prompts, int prompt_ld,
+                          const int32_t* prompt_len, int32_t* out_ids, float* out_logprobs, int32_t* out_steps,
+                          void* stream);
+int wcb_decode_begin_prompted(wcb_handle*, const void* enc, int B, const int32_t* prompts, int prompt_ld,
+                              const int32_t* prompt_len, float bias_boost, int min_new_tokens, wcb_state** out,
+                              void* stream);
 /* HOST, no GPU: out[i] = g(seed, step, v0 + i), the same inline function the kernels compile */
 int wcb_sample_noise(uint64_t seed, int step, int v0, int n, float* out);
 
@@ -492,6 +517,16 @@ int wcb_op_attention(int dtype, const void* q, const void* k, const void* v, voi
  * decode step runs it: the lean form for 16-bit). */
 int wcb_op_attention_decode(int dtype, const void* q, const void* k, const void* v, void* o, int B, int H,
                             int Sk, int nsplit, int variant, void* stream);
+/* the same with a per-row key window (ragged prompts, below): q/o [B][Sq][H*64], the Sq causal queries of a row at
+ * slots Sk-Sq .. Sk-1 (query i sees keys up to its own slot), K/V head-major [B][H][Sk][64]; key_start DEVICE [B]:
+ * the query at slot s of row b attends keys [min(key_start[b], s), s]; keys below the window are never read into
+ * the result (they may be non-finite). variant: 0..5 the prefill kernels of k_attn.hip launch_decode (any Sq),
+ * + 100*n = with n split-KV key chunks (the argument list has no nsplit of its own: the runtime's self-attention
+ * never splits, the chunking is reachable for the kernel tests only); 6 / 7 the one-token kernels of
+ * wcb_op_attention_decode (Sq = 1). key_start = NULL launches the dense kernels on the same arguments (every query
+ * sees keys 0 .. its slot); with every start 0 the windowed result equals theirs bit for bit. */
+int wcb_op_attention_decode_window(int dtype, const void* q, const void* k, const void* v, void* o, int B, int H,
+                                   int Sq, int Sk, const int32_t* key_start, int variant, void* stream);
 
 /* decoder cross-attention in encoder space (k_xenc.hip), the xmode-1 decode path:
  * o[B][d] = Σ_h-blocks W_v,h softmax_j(q'_h · enc_j) enc_j + b_v with q'_h = W_k,hᵀ q_h;

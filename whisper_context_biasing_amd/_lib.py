@@ -117,6 +117,11 @@ SIGNATURES = {
     "wcb_decode_enable_sampling": (C.c_int, [_P, _P, C.c_float, C.POINTER(C.c_uint64)]),
     "wcb_op_lm_head_sample": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                         C.POINTER(C.c_uint64), C.c_int, _P, C.c_long, _P, _P, _P]),
+    "wcb_generate_prompted": (C.c_int, [_P, _P, C.c_int, C.POINTER(WcbGenCfg), C.POINTER(WcbSampleCfg), _P, _P, _P, C.c_int,
+                                        _P, _P, _P, C.POINTER(C.c_int32), _P]),
+    "wcb_decode_begin_prompted": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, C.c_float, C.c_int, C.POINTER(_P), _P]),
+    "wcb_op_attention_decode_window": (C.c_int, [C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P,
+                                                 C.c_int, _P]),
     "wcb_sample_noise": (C.c_int, [C.c_uint64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]),
     "wcb_set_token_rules": (C.c_int, [_P, C.POINTER(WcbTokenRules)]),
     "wcb_token_rules_apply_host": (C.c_int, [C.POINTER(WcbTokenRules), C.c_int, C.c_int, _P, C.c_int, _P]),

@@ -33,8 +33,12 @@ namespace wcb {
 // combines them in chunk order (deterministic) and resets the ticket (cdna_hip_programming.md §6
 // Guideline 16, first row of the measured hand-off table).
 // PHYS (beam search): key j of row b lives in cache row phys[(row0 + b)·phys_ld + j] (k_beam.hip).
-template <typename T, int NW, int U, bool PHYS = false>
+// WIN (ragged prompts): query i of row b attends keys [min(key_start[row0 + b], last), last] of its
+// nk_all keys (last = nk_all - 1, its own slot): every key chunk is cut to the window, and a chunk wholly below it
+// has no key — it publishes l = 0 and the merges below skip it, like a wave or a chunk past the count.
+template <typename T, int NW, int U, bool PHYS = false, bool WIN = false>
 __global__ __launch_bounds__(NW * 64) void attn_decode_kernel(AttnArgs a) {
+  static_assert(!(PHYS && WIN), "the key window is the greedy rows' (keys in place)");
   __shared__ float wo[NW][64];
   __shared__ float wm[NW], wl[NW];
   const int nsplit = a.nsplit > 0 ? a.nsplit : 1;
@@ -45,7 +49,9 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kernel(AttnArgs a) {
   const int seg = lane & 7, kg = lane >> 3;
   const int nk_all = (a.nkeys_dev ? (*a.nkeys_dev + a.nkeys_add) : a.nkeys) + (a.causal ? i : 0);
   const int per = (nk_all + nsplit - 1) / nsplit;
-  const int j_lo = chunk * per, j_hi = min(nk_all, j_lo + per);
+  int j_lo = chunk * per;
+  const int j_hi = min(nk_all, j_lo + per);
+  if constexpr (WIN) j_lo = max(j_lo, max(min(a.key_start[a.row0 + b], nk_all - 1), 0));
   const int nk = max(j_hi - j_lo, 0);
   const T* q = reinterpret_cast<const T*>(a.q) + ((long)b * a.q_Sb + i) * a.ldq + h * 64;
   const long krow = PHYS ? 0L : (long)((a.row0 + b) / a.b_div) * a.k_sb;
@@ -171,8 +177,9 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kernel(AttnArgs a) {
 // scores in LDS, exact max, pass 2 exponentiates, pass 3 streams V. 8 waves, 8 keys per lane group
 // in flight. Measured in the decode graph (2 row groups of 16 rows) slightly ahead of the single-pass
 // kernel above: fewer live registers, more waves per CU.
+// WIN: the key window of attn_decode_kernel; a chunk without a key publishes (-inf, 0).
 constexpr int kMaxKeys = 2048;
-template <typename T, int NW>
+template <typename T, int NW, bool WIN = false>
 __global__ __launch_bounds__(NW * 64) void attn_decode2p_kernel(AttnArgs a) {
   __shared__ float sc[kMaxKeys];
   __shared__ float red[NW][64 + 1];
@@ -185,7 +192,9 @@ __global__ __launch_bounds__(NW * 64) void attn_decode2p_kernel(AttnArgs a) {
   const int seg = lane & 7, kg = lane >> 3;
   const int nk_all = (a.nkeys_dev ? (*a.nkeys_dev + a.nkeys_add) : a.nkeys) + (a.causal ? i : 0);
   const int per = (nk_all + nsplit - 1) / nsplit;
-  const int j_lo = chunk * per, j_hi = min(nk_all, j_lo + per);
+  int j_lo = chunk * per;
+  const int j_hi = min(nk_all, j_lo + per);
+  if constexpr (WIN) j_lo = max(j_lo, max(min(a.key_start[a.row0 + b], nk_all - 1), 0));
   const int nk = max(j_hi - j_lo, 0);
   const T* q = reinterpret_cast<const T*>(a.q) + ((long)b * a.q_Sb + i) * a.ldq + h * 64;
   const long krow = (long)((a.row0 + b) / a.b_div) * a.k_sb;
@@ -324,8 +333,11 @@ __global__ __launch_bounds__(NW * 64) void attn_decode2p_kernel(AttnArgs a) {
 // from it (one dependent round trip per chunk, not one per key group). Skipping the key groups past
 // the device-side count by a branch measured slower (C3 22.8 -> 38.3 µs); clamping their index to the
 // last key (no branch) keeps the loads but collapses them onto one cache line.
-template <typename T, bool PHYS>
+// WIN (ragged prompts): the row attends keys [key_start[row0 + b], nk) — self_attn.h's rule: excluded by select,
+// chunks wholly below the start skipped, the speculative loads and every clamp as in the dense form.
+template <typename T, bool PHYS, bool WIN = false>
 __global__ __launch_bounds__(64) void attn_self_kernel(AttnArgs a) {
+  static_assert(!(PHYS && WIN), "the key window is the greedy rows' (keys in place)");
   const int b = blockIdx.y / a.H, h = blockIdx.y % a.H, lane = threadIdx.x;
   const int seg = lane & 7, kg = lane >> 3;
   const long base = (PHYS ? 0L : (long)((a.row0 + b) / a.b_div) * a.k_sb) + (long)h * a.k_sh + seg * 8;
@@ -361,9 +373,10 @@ __global__ __launch_bounds__(64) void attn_self_kernel(AttnArgs a) {
 #pragma unroll
     for (int u = 0; u < 8; ++u) load8f<T>(vb + koff(min(u * 8 + kg, cap), u), vv[u]);
   }
+  [[maybe_unused]] const int ks = WIN ? max(min(a.key_start[a.row0 + b], nk - 1), 0) : 0;
   float m = -INFINITY, l = 0.f;
   float o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  for (int j0 = 0; j0 < nk; j0 += 64) {
+  for (int j0 = WIN ? (ks & ~63) : 0; j0 < nk; j0 += 64) {
     if (j0) {
       if constexpr (PHYS) pj = prow[min(min(j0 + lane, nk - 1), cap)];
 #pragma unroll
@@ -380,7 +393,8 @@ __global__ __launch_bounds__(64) void attn_self_kernel(AttnArgs a) {
       for (int e = 0; e < 8; ++e) d = fmaf(qv[e], kv[u][e], d);
 #pragma unroll
       for (int x = 1; x < 8; x <<= 1) d += __shfl_xor(d, x, 64);
-      sc[u] = (j0 + u * 8 + kg < nk) ? d : -INFINITY;
+      const int j = j0 + u * 8 + kg;
+      sc[u] = (j < nk && (!WIN || j >= ks)) ? d : -INFINITY;
       mx = fmaxf(mx, sc[u]);
     }
     const float mn = fmaxf(m, wave_max(mx));
@@ -392,7 +406,8 @@ __global__ __launch_bounds__(64) void attn_self_kernel(AttnArgs a) {
     for (int u = 0; u < 8; ++u) {
       // keys past the count were loaded speculatively (rows left by an earlier call, possibly
       // non-finite): they contribute nothing, not even 0·v
-      const bool live = j0 + u * 8 + kg < nk;
+      const int j = j0 + u * 8 + kg;
+      const bool live = j < nk && (!WIN || j >= ks);   // (WIN: nor the keys below the row's start)
       const float p = live ? __expf(sc[u] - mn) : 0.f;
       if (seg == 0) l += p;
 #pragma unroll
@@ -427,16 +442,31 @@ struct SelfLean {
   int ldq, ldo, H, cap, nkeys_add, row0, b_div, npairs;
 };
 
-template <typename T, int WPG = 1>
-__global__ __launch_bounds__(64 * WPG) void attn_self_lean_kernel(SelfLean a) {
+// ragged prompts: the compact block with the per-row key starts behind it (the dense kernel's argument block stays
+// the one it was)
+struct SelfLeanWin : SelfLean {
+  const int* key_start;   // [rows] first key of every row's window (absolute rows: row0 + b)
+};
+
+template <typename T, int WPG = 1, typename Args = SelfLean>
+__global__ __launch_bounds__(64 * WPG) void attn_self_lean_kernel(Args a) {
   // WPG (row, head) pairs per workgroup, one per wave (pairs past the batch re-run the last one)
   const int pair = min(blockIdx.y * WPG + (int)(threadIdx.x >> 6), a.npairs - 1);
   const int b = pair / a.H, h = pair % a.H;
   const long base = (long)((a.row0 + b) / a.b_div) * a.k_sb + (long)h * a.k_sh;
-  self_attn_wave<T>(reinterpret_cast<const T*>(a.q) + (long)b * a.ldq + h * 64,
-                           reinterpret_cast<const T*>(a.k) + base, reinterpret_cast<const T*>(a.v) + base, a.cap,
-                           [&] { return __builtin_amdgcn_readfirstlane(__builtin_nontemporal_load(a.nkeys_dev)) + a.nkeys_add; },
-                           reinterpret_cast<T*>(a.o) + (long)b * a.ldo + h * 64);
+  auto nkeys = [&] { return __builtin_amdgcn_readfirstlane(__builtin_nontemporal_load(a.nkeys_dev)) + a.nkeys_add; };
+  if constexpr (__is_same(Args, SelfLeanWin)) {
+    // the row's start is requested right behind the key count: one more scalar in the same round trip
+    self_attn_wave<T, true>(reinterpret_cast<const T*>(a.q) + (long)b * a.ldq + h * 64,
+                            reinterpret_cast<const T*>(a.k) + base, reinterpret_cast<const T*>(a.v) + base, a.cap, nkeys,
+                            reinterpret_cast<T*>(a.o) + (long)b * a.ldo + h * 64, [&] {
+                              return __builtin_amdgcn_readfirstlane(__builtin_nontemporal_load(a.key_start + a.row0 + b));
+                            });
+  } else {
+    self_attn_wave<T>(reinterpret_cast<const T*>(a.q) + (long)b * a.ldq + h * 64,
+                      reinterpret_cast<const T*>(a.k) + base, reinterpret_cast<const T*>(a.v) + base, a.cap, nkeys,
+                      reinterpret_cast<T*>(a.o) + (long)b * a.ldo + h * 64);
+  }
 }
 
 template <typename T>
@@ -450,15 +480,34 @@ static void launch_decode(const AttnArgs& b, dim3 grid, int variant, hipStream_t
       c.npairs = (int)grid.y;
       // one (row, head) pair per 64-thread workgroup (4 per 256-thread workgroup measured 0.5 ms slower per
       // 72-token C2 call, tools/decode_ab.py)
-      WCB_LAUNCH((attn_self_lean_kernel<T, 1>), dim3(1, grid.y), dim3(64), 0, s, c);
+      if (b.key_start) {
+        SelfLeanWin cw;
+        static_cast<SelfLean&>(cw) = c;
+        cw.key_start = b.key_start;
+        WCB_LAUNCH((attn_self_lean_kernel<T, 1, SelfLeanWin>), dim3(1, grid.y), dim3(64), 0, s, cw);
+      } else {
+        WCB_LAUNCH((attn_self_lean_kernel<T, 1>), dim3(1, grid.y), dim3(64), 0, s, c);
+      }
       return;
     }
     if (b.phys) WCB_LAUNCH((attn_self_kernel<T, true>), dim3(1, grid.y), dim3(64), 0, s, b);
+    else if (b.key_start) WCB_LAUNCH((attn_self_kernel<T, false, true>), dim3(1, grid.y), dim3(64), 0, s, b);
     else WCB_LAUNCH((attn_self_kernel<T, false>), dim3(1, grid.y), dim3(64), 0, s, b);
     return;
   }
   if (b.phys) {   // beam-search self-attention: keys through the row map
     WCB_LAUNCH((attn_decode_kernel<T, 4, 8, true>), grid, dim3(256), 0, s, b);
+    return;
+  }
+  if (b.key_start) {   // ragged prompts (causal prefill): the same variants with the per-row key window
+    switch (variant) {
+      case 0: WCB_LAUNCH((attn_decode2p_kernel<T, 8, true>), grid, dim3(512), 0, s, b); break;
+      case 1: WCB_LAUNCH((attn_decode_kernel<T, 4, 8, false, true>), grid, dim3(256), 0, s, b); break;
+      case 2: WCB_LAUNCH((attn_decode_kernel<T, 4, 4, false, true>), grid, dim3(256), 0, s, b); break;
+      case 3: WCB_LAUNCH((attn_decode_kernel<T, 8, 4, false, true>), grid, dim3(512), 0, s, b); break;
+      case 4: WCB_LAUNCH((attn_decode_kernel<T, 8, 8, false, true>), grid, dim3(512), 0, s, b); break;
+      default: WCB_LAUNCH((attn_decode_kernel<T, 16, 4, false, true>), grid, dim3(1024), 0, s, b); break;
+    }
     return;
   }
   switch (variant) {

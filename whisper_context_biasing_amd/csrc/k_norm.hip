@@ -79,13 +79,16 @@ void layernorm(DType t, const float* x, const float* w, const float* b, void* y,
 
 // also publishes the per-16-column partial sums (Σx, Σx²) of the new row for the fused LayerNorm
 // of the first decoder GEMM (deterministic fixed-order sums, see k_gemm.hip st_in)
-template <typename T>
+// RAG (ragged prompts): decoder row row / rps starts pos_off[row / rps] slots late — its position is the slot
+// minus that, clamped to the table (a dead slot reads position 0; nothing reads what it computes)
+template <typename T, bool RAG = false>
 __global__ __launch_bounds__(256) void embed_kernel(const T* __restrict__ emb, const T* __restrict__ pemb, const int* __restrict__ ids,
                                                     const int* __restrict__ pos, float* __restrict__ x, float* __restrict__ st,
                                                     int M, int d, T* __restrict__ x16, int V, int rps, int st_w,
-                                                    T* __restrict__ x16fm, int fm_nw, int fm_kpw) {
+                                                    T* __restrict__ x16fm, int fm_nw, int fm_kpw,
+                                                    const int* __restrict__ pos_off, int n_pos) {
   const int row = blockIdx.x;
-  const int p = *pos + row % rps;
+  const int p = RAG ? max(min(*pos + row % rps - pos_off[row / rps], n_pos - 1), 0) : *pos + row % rps;
   const int raw = ids[row];
   const long id = raw >= 0 && raw < V ? raw : 0;   // never index past the table (ids are produced on device)
   for (int c0 = 0; c0 < d; c0 += 256) {
@@ -119,17 +122,29 @@ __global__ __launch_bounds__(256) void embed_kernel(const T* __restrict__ emb, c
 }
 
 void embed(DType t, const void* emb, const void* pemb, const int* ids, const int* pos, float* x, float* st, int M,
-           int d, hipStream_t s, void* x16, int V, int rps, int st_w, void* x16fm) {
+           int d, hipStream_t s, void* x16, int V, int rps, int st_w, void* x16fm, const int* pos_off, int n_pos) {
   rps = rps > 1 ? rps : 1;
   int nw = 0, kpw = 0;
   if (x16fm && !lean_cfg(d, nw, kpw)) x16fm = nullptr;
+  const int* po = pos_off;
+  if (po) {
+    switch (t) {
+      case kBF16: WCB_LAUNCH((embed_kernel<bf16_t, true>), dim3(M), dim3(256), 0, s, (const bf16_t*)emb,
+                                     (const bf16_t*)pemb, ids, pos, x, st, M, d, (bf16_t*)x16, V, rps, st_w, (bf16_t*)x16fm, nw, kpw, po, n_pos); break;
+      case kF16: WCB_LAUNCH((embed_kernel<f16_t, true>), dim3(M), dim3(256), 0, s, (const f16_t*)emb,
+                                    (const f16_t*)pemb, ids, pos, x, st, M, d, (f16_t*)x16, V, rps, st_w, (f16_t*)x16fm, nw, kpw, po, n_pos); break;
+      case kF32: WCB_LAUNCH((embed_kernel<float, true>), dim3(M), dim3(256), 0, s, (const float*)emb,
+                                    (const float*)pemb, ids, pos, x, st, M, d, (float*)x16, V, rps, st_w, (float*)nullptr, 0, 0, po, n_pos); break;
+    }
+    return;
+  }
   switch (t) {
     case kBF16: WCB_LAUNCH(embed_kernel<bf16_t>, dim3(M), dim3(256), 0, s, (const bf16_t*)emb,
-                                   (const bf16_t*)pemb, ids, pos, x, st, M, d, (bf16_t*)x16, V, rps, st_w, (bf16_t*)x16fm, nw, kpw); break;
+                                   (const bf16_t*)pemb, ids, pos, x, st, M, d, (bf16_t*)x16, V, rps, st_w, (bf16_t*)x16fm, nw, kpw, po, 0); break;
     case kF16: WCB_LAUNCH(embed_kernel<f16_t>, dim3(M), dim3(256), 0, s, (const f16_t*)emb,
-                                  (const f16_t*)pemb, ids, pos, x, st, M, d, (f16_t*)x16, V, rps, st_w, (f16_t*)x16fm, nw, kpw); break;
+                                  (const f16_t*)pemb, ids, pos, x, st, M, d, (f16_t*)x16, V, rps, st_w, (f16_t*)x16fm, nw, kpw, po, 0); break;
     case kF32: WCB_LAUNCH(embed_kernel<float>, dim3(M), dim3(256), 0, s, (const float*)emb,
-                                  (const float*)pemb, ids, pos, x, st, M, d, (float*)x16, V, rps, st_w, (float*)nullptr, 0, 0); break;
+                                  (const float*)pemb, ids, pos, x, st, M, d, (float*)x16, V, rps, st_w, (float*)nullptr, 0, 0, po, 0); break;
   }
 }
 

@@ -104,7 +104,8 @@ __global__ __launch_bounds__(256) void select_partial_kernel(SelectArgs a) {
 // One wave per row; the last row to finish (atomic ticket) advances the step/position counters.
 // EMB: the row's next-step input embedding in the same launch (k_norm.hip embed_kernel's arithmetic and
 // stats grouping, 64 columns per pass).
-template <typename T, bool EMB, bool FOREST, bool SAMPLE = false>
+// RAG (ragged prompts, with EMB): the row's next position is the next slot minus the row's prompt offset.
+template <typename T, bool EMB, bool FOREST, bool SAMPLE = false, bool RAG = false>
 __global__ __launch_bounds__(64) void select_finalize_kernel(SelectArgs a) {
   const int m = blockIdx.x, lane = threadIdx.x;
   const int step = *a.step;
@@ -220,7 +221,7 @@ __global__ __launch_bounds__(64) void select_finalize_kernel(SelectArgs a) {
   if constexpr (EMB) {
     // 8 consecutive columns per lane (16-byte accesses of T; the fragment-major copy holds them
     // contiguously too), the optional per-st_w-column partials in embed_kernel's lane-butterfly order
-    const int d = a.d, p = min(pos0 + 1, a.n_pos - 1);
+    const int d = a.d, p = RAG ? max(min(pos0 + 1 - a.pos_off[m], a.n_pos - 1), 0) : min(pos0 + 1, a.n_pos - 1);
     const T* er = reinterpret_cast<const T*>(a.emb) + (long)tok * d;
     const T* pr = reinterpret_cast<const T*>(a.pemb) + (long)p * d;
     if (a.st) {   // (older skinny consumers only) one column per lane, as embed_kernel
@@ -343,7 +344,11 @@ void write_i32(int* dst, const int* host_src, int n, hipStream_t s) {
 
 template <bool FOREST, bool SAMPLE>
 static void select_finalize_launch(const SelectArgs& a, hipStream_t s) {
-  if (!a.emb) {
+  if (a.emb && a.pos_off) {   // ragged prompts: the embedding at the row's own position
+    if (a.dtype == kBF16) WCB_LAUNCH((select_finalize_kernel<bf16_t, true, FOREST, SAMPLE, true>), dim3(a.M), dim3(64), 0, s, a);
+    else if (a.dtype == kF16) WCB_LAUNCH((select_finalize_kernel<f16_t, true, FOREST, SAMPLE, true>), dim3(a.M), dim3(64), 0, s, a);
+    else WCB_LAUNCH((select_finalize_kernel<float, true, FOREST, SAMPLE, true>), dim3(a.M), dim3(64), 0, s, a);
+  } else if (!a.emb) {
     WCB_LAUNCH((select_finalize_kernel<float, false, FOREST, SAMPLE>), dim3(a.M), dim3(64), 0, s, a);
   } else if (a.dtype == kBF16) {
     WCB_LAUNCH((select_finalize_kernel<bf16_t, true, FOREST, SAMPLE>), dim3(a.M), dim3(64), 0, s, a);

@@ -155,9 +155,11 @@ void layernorm(DType t, const float* x, const float* w, const float* b, void* y,
 // stats: per-st_w-column partial sums (Σx, Σx²) of the new rows (16: the older skinny consumers; 32:
 // the ring tiles' folded LayerNorm, GemmArgs::rst_in)
 // x16fm: also the 16-bit rows in the fragment-major layout of the lean LN-fused projections (lean_cfg(d))
+// pos_off (ragged prompts, nullable): decoder row r / rows_per_seq reads position clamp(*pos + r_pos − pos_off[row],
+// 0, n_pos − 1) — its prompt starts pos_off[row] slots late
 void embed(DType t, const void* emb, const void* pos_emb, const int* ids, const int* pos, float* x,
            float* stats, int M, int d, hipStream_t s, void* x16 = nullptr, int V = 1 << 30, int rps = 1, int st_w = 16,
-           void* x16fm = nullptr);
+           void* x16fm = nullptr, const int* pos_off = nullptr, int n_pos = 0);
 // prefill: ids[r·np + t] = src[r·ld + *pos + t] (ld 0: one prefix row shared by every row)
 void prefill_ids(int* ids, const int* src, int R, int np, int ld, const int* pos, hipStream_t s);
 void add_i32(int* p, int v, hipStream_t s);   // *p += v (one thread)
@@ -197,6 +199,10 @@ struct AttnArgs {
                      // (they share its K/V through that XCD's L2); requires B·H % 8 == 0
   int kv_rows = 0;   // > 0: K/V rows allocated per (row, head) — the one-token self-attention kernel
                      // loads the first keys before the device key count arrives, clamped to this
+  // ragged prompts (decode kernels, keys in place): row b attends keys from key_start[row0 + b]
+  // (device [rows]; clamped to its last key, so a dead prompt slot sees itself) — the windowed instantiations.
+  // Null: the dense kernels as they always were
+  const int* key_start = nullptr;
 };
 void attention_decode(DType t, const AttnArgs& a, hipStream_t s);   // VALU, any T, any Sq
 bool attention_flash(DType t, const AttnArgs& a, hipStream_t s);    // MFMA encoder (16-bit T)
@@ -286,6 +292,8 @@ struct SelectArgs {
   const void* emb = nullptr; const void* pemb = nullptr; int n_pos = 0, d = 0, dtype = 0;
   float* x = nullptr; void* x16 = nullptr; void* x16fm = nullptr; int fm_nw = 0, fm_kpw = 0;
   float* st = nullptr; int st_w = 16;
+  // ragged prompts (nullable, with emb): row m's next position is clamp(pos + 1 − pos_off[m], 0, n_pos − 1)
+  const int* pos_off = nullptr;
   // per-utterance lists (forest.root non-null): row m is clip m; root_bits must then be all zero
   ForestArgs forest;
   // temperature sampling (seeds non-null: [M] per-row seeds, *inv_t = 1 / T; sample.h): the partials were

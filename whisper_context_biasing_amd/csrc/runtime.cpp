@@ -152,6 +152,7 @@ struct wcb_state {
   ForestDev fd;
   bool logprobs = false; // wcb_decode_enable_logprobs: every step also writes its column of the context's lpbuf
   bool sampling = false; // wcb_decode_enable_sampling: every step draws its tokens (the context's samp words)
+  bool ragged = false;   // per-clip prompts of different lengths (left-padded to P): every step reads the context's poff
 };
 
 // lean decode projection classes stamped inside the replayed decode graph (stamps pass), by region
@@ -218,6 +219,15 @@ struct DecCtx {
   size_t f_stage_words = 0;
   hipEvent_t ev_fcopy = nullptr;
   bool f_copy_pending = false;
+  // ragged prompts (wcb_generate_prompted, wcb_decode_begin_prompted): poff = the slot offset
+  // Pmax − P_b of every row [kPromptRows], allocated once and never moved (the ragged graphs hold its address, the
+  // graph key only the fact); the left-padded prompts and the offsets go up on the decode stream from the pinned
+  // p_stage, as the forest does
+  DevBuf poff;
+  int* p_stage = nullptr;
+  size_t p_stage_words = 0;
+  hipEvent_t ev_pcopy = nullptr;
+  bool p_copy_pending = false;
 };
 
 struct wcb_handle {
@@ -710,6 +720,9 @@ void wcb_destroy(wcb_handle* h) {
       if (e) (void)hipEventDestroy(e);
     if (D.done_h) (void)hipHostFree(D.done_h);
     D.forest.release();
+    D.poff.release();
+    if (D.p_stage) (void)hipHostFree(D.p_stage);
+    if (D.ev_pcopy) (void)hipEventDestroy(D.ev_pcopy);
     if (D.f_stage) (void)hipHostFree(D.f_stage);
     if (D.ev_fcopy) (void)hipEventDestroy(D.ev_fcopy);
     for (int i = 0; i < DecCtx::kMaxSub; ++i) {
@@ -1415,6 +1428,9 @@ struct StepCfg {
   // token timestamps: a teacher-forced pass (rps > 1, all rows in one chain) also captures the cross-attention
   // weights of the selected heads. Null: the pass as it always was
   const struct AlignPass* align = nullptr;
+  // greedy, ragged prompts: the slot offset of every row (the context's poff) — the self-attention windows and the
+  // position embeddings shift by it. Null: the step as it always was
+  const int* pos_off = nullptr;
 };
 
 // the capture of one teacher-forced pass of wcb_align: per layer the selected (head, slot in the list) pairs; the
@@ -1612,6 +1628,7 @@ void decode_rows(wcb_handle* h, const StepCfg& c, int b0, int nb, int chain, hip
     a.row0 = b0; a.phys = c.phys; a.phys_ld = T;
     a.o = datt; a.ldo = d; a.o_Sb = rps; a.B = nb; a.H = H; a.nkeys_dev = pos; a.nkeys_add = 1;
     a.kv_rows = rps == 1 ? T : 0;
+    a.key_start = c.pos_off;   // ragged prompts: row b0 + b attends from its own first slot (null: every key)
     {
       const double t_keys = c.host_pos >= 0 ? c.host_pos + 1 : 0;   // keys this step (eager pass)
       h->timed("dec_self_attn", 4.0 * nb * H * t_keys * 64, nb * H * t_keys * 128.0 * e, st_,
@@ -1795,7 +1812,7 @@ void step_embed(wcb_handle* h, const StepCfg& c) {
   h->timed("dec_embed", 0, (double)B * d * (2.0 * esize(h->d.dtype) + 4), D.hs, [&] {
     embed(h->dt, h->tok_emb, h->dec_pos, RowInts(D, B).next, ints + I_POS, D.dx.as<float>(),
           !h->dec_gemm ? D.dstats.as<float>() : r32 ? D.drst.as<float>() : nullptr, B, d, D.hs, D.dx16.p, h->d.vocab, 1,
-          r32 ? 32 : 16, xfm_possible(h) ? D.dx16fm.p : nullptr);
+          r32 ? 32 : 16, xfm_possible(h) ? D.dx16fm.p : nullptr, c.pos_off, h->d.n_text_ctx);
   });
 }
 
@@ -1848,6 +1865,7 @@ void decode_step(wcb_handle* h, const StepCfg& c) {
     if (c.embedded) {   // the next step's input embedding in the same launch (embed()'s outputs)
       const bool r32 = h->dec_gemm && lnf_possible(h);
       s.emb = h->tok_emb; s.pemb = h->dec_pos; s.n_pos = h->d.n_text_ctx; s.d = d; s.dtype = h->dt;
+      s.pos_off = c.pos_off;
       s.x = D.dx.as<float>(); s.x16 = D.dx16.p;
       // (greedy decodes <= 64 rows: the decode-GEMM consumers compute their own LayerNorm statistics, so
       // the 32-column partials of the > 64-row folded path are not published; the older skinny consumers
@@ -1881,7 +1899,7 @@ void prefill_step(wcb_handle* h, StepCfg c, int np, const int* src, int ld) {
     prefill_ids(D.pids.as<int>(), src, R, np, ld, pos, D.hs);
     const bool r32 = h->dec_gemm && lnf_possible(h);
     embed(h->dt, h->tok_emb, h->dec_pos, D.pids.as<int>(), pos, D.dx.as<float>(), r32 ? D.drst.as<float>() : nullptr, M,
-          d, D.hs, D.dx16.p, h->d.vocab, np, 32, xfm_possible(h) ? D.dx16fm.p : nullptr);
+          d, D.hs, D.dx16.p, h->d.vocab, np, 32, xfm_possible(h) ? D.dx16fm.p : nullptr, c.pos_off, h->d.n_text_ctx);
   });
   decode_rows(h, c, 0, R, 0, D.hs);
   add_i32(pos, np, D.hs);
@@ -1974,6 +1992,50 @@ ForestDev install_forest(wcb_handle* h, DecCtx& D, const wcb_bias_batch* bb) {
   return F;
 }
 
+// Per-clip prompts of different lengths: clip b's P_b = plen[b] prompt tokens (the start token last)
+// live in slots off_b = P − P_b .. P − 1 of the context's P-wide prompt rows (D.forced), the slots before them hold the
+// pad token (whatever the caller's array has there), and off_b goes into D.poff. Both go up on the decode stream from
+// pinned staging, so the caller's arrays are free on return (async_out included) and a replayed graph never sees half
+// an upload. Returns whether any clip is shorter than P (false: the dense kernels decode the call). The lengths were
+// checked by the caller.
+constexpr int kPromptRows = 64;
+bool install_prompts(wcb_handle* h, DecCtx& D, const int32_t* prompts, int P, const int32_t* plen, int B) {
+  const size_t np = (size_t)B * P, words = np + kPromptRows;
+  if (!D.ev_pcopy) HIPCHK(hipEventCreateWithFlags(&D.ev_pcopy, hipEventDisableTiming));
+  if (D.p_copy_pending) { HIPCHK(hipEventSynchronize(D.ev_pcopy)); D.p_copy_pending = false; }
+  if (words > D.p_stage_words) {
+    if (D.p_stage) (void)hipHostFree(D.p_stage);
+    D.p_stage = nullptr;
+    D.p_stage_words = 0;
+    const size_t cap = std::max<size_t>(words * 2, 1 << 12);
+    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&D.p_stage), cap * 4, hipHostMallocDefault));
+    D.p_stage_words = cap;
+  }
+  if (np * 4 > D.forced.bytes) { quiesce(h); D.forced.ensure(np * 4); }
+  D.poff.ensure((size_t)kPromptRows * 4);   // once: the address the ragged graphs hold
+  int* offs = D.p_stage + np;
+  bool ragged = false;
+  for (int b = 0; b < kPromptRows; ++b) offs[b] = b < B ? P - plen[b] : 0;
+  for (int b = 0; b < B; ++b) {
+    ragged |= offs[b] > 0;
+    for (int s = 0; s < P; ++s) D.p_stage[(size_t)b * P + s] = s < offs[b] ? h->d.pad_token_id : prompts[(size_t)b * P + s];
+  }
+  HIPCHK(hipMemcpyAsync(D.forced.p, D.p_stage, np * 4, hipMemcpyHostToDevice, D.hs));
+  HIPCHK(hipMemcpyAsync(D.poff.p, offs, (size_t)kPromptRows * 4, hipMemcpyHostToDevice, D.hs));
+  HIPCHK(hipEventRecord(D.ev_pcopy, D.hs));
+  D.p_copy_pending = true;
+  return ragged;
+}
+void check_prompts(const int32_t* prompts, int prompt_ld, const int32_t* prompt_len, int B, int nb) {
+  REQUIRE(prompts && prompt_len && prompt_ld >= 1, "prompts, prompt_len and prompt_ld >= 1 are required");
+  for (int b = 0; b < B; ++b)
+    REQUIRE(prompt_len[b] >= 1 && prompt_len[b] <= prompt_ld,
+            "prompt_len[" + std::to_string(b) + "] = " + std::to_string(prompt_len[b]) + " outside [1, prompt_ld = " +
+                std::to_string(prompt_ld) + "] (the start token counts)");
+  if (nb > 1)
+    throw WcbError(WCB_ERR_UNSUPPORTED, "per-clip prompts are greedy only (num_beams = 1): beam scores count the prompt");
+}
+
 // Temperature sampling of a decode in context D: inv_T = 1 / T and the per-row seeds into the context's samp
 // words, stream-ordered on the decode stream and passed by value (write_i32: the caller's array is not read
 // after the call returns, async_out and several contexts in flight included). The allocation is made once.
@@ -2037,17 +2099,21 @@ void prefill_range(wcb_handle* h, const StepCfg& sc, const int* src, int ld, int
 // The start of decode `st` in context buf, on its stream: the int block zeroed, the prompt uploaded — `shared`: one
 // host row [P] for every decoder row (row stride 0), else [B][P], clip b's on each of its beam rows; null: the
 // start token — the beam state initialised (before the prefill: its self-attention reads keys through bm.phys),
-// and the configuration every pass of the decode starts from
-StepCfg decode_start(wcb_handle* h, int buf, wcb_state& st, const int32_t* prefix, bool shared, const wcb_bias* bs) {
+// and the configuration every pass of the decode starts from. plen (greedy, with prefix [B][P] left-padded): the
+// per-clip prompt lengths — install_prompts
+StepCfg decode_start(wcb_handle* h, int buf, wcb_state& st, const int32_t* prefix, bool shared, const wcb_bias* bs,
+                     const int32_t* plen = nullptr) {
   DecCtx& D = h->dc[buf];
   const int R = st.B * st.nb, P = st.P;
   HIPCHK(hipMemsetAsync(D.ints.p, 0, RowInts::words(R) * 4, D.hs));   // (the rule state with finished[])
   std::vector<int32_t> rows;
-  if (prefix && !shared)
+  if (prefix && !shared && !plen)
     for (int r = 0; r < R; ++r) rows.insert(rows.end(), prefix + (size_t)(r / st.nb) * P, prefix + (size_t)(r / st.nb + 1) * P);
   const size_t pbytes = (shared ? (size_t)P : rows.size()) * 4;
   if (prefix && pbytes > D.forced.bytes) { quiesce(h); D.forced.ensure(pbytes); }
-  if (!prefix) {
+  if (plen) {   // (greedy: one row per clip)
+    st.ragged = install_prompts(h, D, prefix, P, plen, st.B);
+  } else if (!prefix) {
     fill_i32(RowInts(D, R).next, h->d.decoder_start_token_id, R, D.hs);
   } else if (shared) {
     write_i32(D.forced.as<int>(), prefix, P, D.hs);
@@ -2064,6 +2130,7 @@ StepCfg decode_start(wcb_handle* h, int buf, wcb_state& st, const int32_t* prefi
   sc.forced = D.forced.as<int>(); sc.forced_ld = shared ? 0 : P;
   sc.clips = st.B; sc.nb = st.nb; sc.xmode = st.xmode;
   if (st.nb > 1) { sc.phys = st.bm.phys; sc.beam = &st.bm; }
+  if (st.ragged) sc.pos_off = D.poff.as<int>();
   return sc;
 }
 
@@ -2116,6 +2183,8 @@ struct GenCall {
   const wcb_bias* bias = nullptr; const wcb_bias_batch* bb = nullptr;
   float *out_logprobs = nullptr, *out_seq_scores = nullptr;
   const wcb_sample_cfg* smp = nullptr;
+  // per-clip prompts (wcb_generate_prompted): HOST [B][prompt_ld] left-padded, lengths HOST [B]; prefix is then null
+  const int32_t* prompts = nullptr; int prompt_ld = 0; const int32_t* prompt_len = nullptr;
 };
 
 // the step-wise decode context, after the check every step-wise entry point makes of its state (`what`: the
@@ -2185,7 +2254,9 @@ static void generate_impl(wcb_handle* h, const GenCall& c) {
     REQUIRE(cfg->bias_boost >= 0.f, "bias_boost must be >= 0");
     REQUIRE(cfg->max_new_tokens >= 1, "max_new_tokens must be >= 1");
     REQUIRE(c.mel != nullptr, "mel is required");
-    const int P = c.prefix ? c.prefix_len : 1;
+    const bool prompted = c.prompts || c.prompt_len;
+    if (prompted) check_prompts(c.prompts, c.prompt_ld, c.prompt_len, B, nb);
+    const int P = prompted ? c.prompt_ld : c.prefix ? c.prefix_len : 1;
     REQUIRE(P >= 1, "prefix_len must be >= 1");
     const int T = P + cfg->max_new_tokens;
     REQUIRE(T <= h->d.n_text_ctx + 1, "prefix + max_new_tokens exceeds max_target_positions");
@@ -2231,7 +2302,8 @@ static void generate_impl(wcb_handle* h, const GenCall& c) {
     wcb_state st;
     st.h = h; st.B = B; st.nb = nb; st.P = P; st.T = Tc; st.max_new = max_new; st.min_new = cfg->min_new_tokens;
     st.lam = cfg->bias_boost; st.xmode = xm;
-    StepCfg sc = decode_start(h, buf, st, c.prefix, /*shared=*/true, bs);
+    StepCfg sc = prompted ? decode_start(h, buf, st, c.prompts, /*shared=*/false, bs, c.prompt_len)
+                          : decode_start(h, buf, st, c.prefix, /*shared=*/true, bs);
     BeamArgs& bm = st.bm;
     if (bb) {   // per-utterance lists
       start_forest(h, D, st, bb);
@@ -2245,7 +2317,7 @@ static void generate_impl(wcb_handle* h, const GenCall& c) {
     if (smp) sc.samp = install_sampling(D, smp->temperature, smp->seeds, R);
     const bool ruled = nb == 1 && h->rules_on;
     if (ruled) apply_rules(h, sc);
-    decode_prompt(h, sc, P, c.prefix != nullptr);
+    decode_prompt(h, sc, P, c.prefix != nullptr || prompted);
     sc.lm_head = true;
     sc.select = true;
     sc.embedded = nb == 1;   // greedy: decode_prompt embedded the first step's input
@@ -2257,7 +2329,9 @@ static void generate_impl(wcb_handle* h, const GenCall& c) {
     int kn = snprintf(key, sizeof key, "%d/%d/%d/%d/%s/%a/%d/%d/%d/%d", B, nb, Tc, out_ld, bkey,
                       cfg->bias_boost, cfg->min_new_tokens, h->n_sub, (int)h->prof_stamps, P);
     if (ruled)   // what a ruled graph bakes in beside the bitmaps' stable addresses
-      snprintf(key + kn, sizeof key - kn, "/R%d.%d.%d.%d", sc.ts.on, sc.ts.ts0, sc.ts.max_init, (int)h->rules_has0);
+      kn += snprintf(key + kn, sizeof key - kn, "/R%d.%d.%d.%d", sc.ts.on, sc.ts.ts0, sc.ts.max_init, (int)h->rules_has0);
+    if (st.ragged)   // ragged prompts: the windowed kernels reading the context's offsets — the fact, never the lengths
+      snprintf(key + kn, sizeof key - kn, "/G");
     // per-launch HIP events (profiling bit 0) cannot bracket nodes of a replayed graph: eager launches
     const bool use_graph = cfg->use_graph && !h->prof;
     // The decode step replays as a hipGraph; steps_per_graph steps are captured into one graph so the
@@ -2380,6 +2454,19 @@ int wcb_generate_sampled(wcb_handle* h, const float* mel, int B, const wcb_gen_c
   });
 }
 
+int wcb_generate_prompted(wcb_handle* h, const float* mel, int B, const wcb_gen_cfg* cfg, const wcb_sample_cfg* smp,
+                          const wcb_bias* bias, const wcb_bias_batch* bb, const int32_t* prompts, int prompt_ld,
+                          const int32_t* prompt_len, int32_t* out_ids, float* out_logprobs, int32_t* out_steps, void* stream) {
+  return guarded(h, [&] {
+    REQUIRE(h && cfg, "bad argument");
+    REQUIRE(!(bias && bb), "wcb_generate_prompted: a shared automaton or a bias batch, not both");
+    REQUIRE(prompts && prompt_len, "wcb_generate_prompted: prompts and prompt_len are required (wcb_generate_sampled decodes one shared prompt)");
+    GenCall c{mel, B, cfg, nullptr, 1, out_ids, out_steps, stream, bias, bb, out_logprobs, nullptr, smp};
+    c.prompts = prompts; c.prompt_ld = prompt_ld; c.prompt_len = prompt_len;
+    generate_impl(h, c);
+  });
+}
+
 // ---- step-wise greedy decoding (SURVEY §8(b) wcb_decode_begin / wcb_decode_step): the decode step
 // of wcb_generate, one token per call, on the decode context kMaxCtx-1 (its own stream and buffers,
 // so generate() calls on contexts 0 .. nctx-1 are unaffected); eager launches (the caller inspects
@@ -2388,9 +2475,12 @@ int wcb_generate_sampled(wcb_handle* h, const float* mel, int B, const wcb_gen_c
 // begin (greedy, nb = 1, or the beam path of wcb_generate, nb >= 2): the given encoder output into the context,
 // the per-clip prefix prefilled on every row of the clip, the first step's input ready; the length cap is
 // prefix + max_new_tokens, at most max_target_positions (generate()'s)
+// plen (wcb_decode_begin_prompted): prefix = the per-clip prompts [B][prefix_len] left-padded, plen their lengths
 static void decode_begin(wcb_handle* h, const void* enc, int B, int nb, const int32_t* prefix, int prefix_len,
-                         int max_new_tokens, float bias_boost, int min_new_tokens, wcb_state** out, void* stream) {
+                         int max_new_tokens, float bias_boost, int min_new_tokens, wcb_state** out, void* stream,
+                         const int32_t* plen = nullptr, bool prompted = false) {
   REQUIRE(h && enc && out && B > 0 && B <= 64, "bad argument (1 <= B <= 64, enc and out required)");
+  if (prompted) check_prompts(prefix, prefix_len, plen, B, nb);
   if (!h->ready) throw WcbError(WCB_ERR_STATE, "weights not finalized");
   if (nb < 1) throw WcbError(WCB_ERR_ARG, "num_beams must be >= 1");
   REQUIRE(nb <= kMaxBeams, "num_beams must be in [2, 8] (greedy: num_beams = 1)");
@@ -2418,7 +2508,7 @@ static void decode_begin(wcb_handle* h, const void* enc, int B, int nb, const in
   sync_in(h, stream, D.hs);
   // the caller's encoder output [B][1500][d] (model dtype) is copied / projected into owned buffers
   enc_to_ctx(h, ci, enc, B, st->xmode, D.hs, stream);
-  const StepCfg sc = decode_start(h, ci, *st, prefix, /*shared=*/false, h->empty_bias.get());
+  const StepCfg sc = decode_start(h, ci, *st, prefix, /*shared=*/false, h->empty_bias.get(), plen);
   decode_prompt(h, sc, P, prefix != nullptr);
   HIPCHK(hipStreamSynchronize(D.hs));
   h->step_state = st.release();
@@ -2430,6 +2520,14 @@ int wcb_decode_begin(wcb_handle* h, const void* enc, int B, int num_beams, const
                      float bias_boost, int min_new_tokens, wcb_state** out, void* stream) {
   return guarded(h, [&] {   // to the default length cap (generate()'s max_length 448)
     decode_begin(h, enc, B, num_beams, prefix, prefix_len, h ? h->d.n_text_ctx : 0, bias_boost, min_new_tokens, out, stream);
+  });
+}
+
+int wcb_decode_begin_prompted(wcb_handle* h, const void* enc, int B, const int32_t* prompts, int prompt_ld,
+                              const int32_t* prompt_len, float bias_boost, int min_new_tokens, wcb_state** out, void* stream) {
+  return guarded(h, [&] {   // greedy, to the default length cap as wcb_decode_begin
+    decode_begin(h, enc, B, 1, prompts, prompt_ld, h ? h->d.n_text_ctx : 0, bias_boost, min_new_tokens, out, stream, prompt_len,
+                 /*prompted=*/true);
   });
 }
 
@@ -2473,6 +2571,7 @@ int wcb_decode_step(wcb_handle* h, wcb_state* st, const wcb_bias* bias, int32_t*
       sc.embedded = true;   // (wcb_decode_begin embedded the first input; each finalize embeds the next)
       if (st->logprobs) sc.logprob_out = D.lpbuf.as<float>();
       if (st->sampling) sc.samp = D.samp.as<uint64_t>();
+      if (st->ragged) sc.pos_off = D.poff.as<int>();
       apply_rules(h, sc);   // (fixed for the whole decode: wcb_set_token_rules is refused while the state is open)
     }
     if (st->forest) sc.forest = &st->fd;
@@ -3558,6 +3657,40 @@ int wcb_op_attention_decode(int dtype, const void* q, const void* k, const void*
       a.nsplit = nsplit;
       part.ensure((size_t)B * H * nsplit * 66 * 4);
       ticket.ensure((size_t)B * H * 4);
+      a.part = part.as<float>();
+      a.ticket = ticket.as<int>();
+    }
+    attention_decode(DType(dtype), a, (hipStream_t)stream);
+    if (nk_dev) HIPCHK(hipFreeAsync(nk_dev, (hipStream_t)stream));
+    HIPCHK(hipGetLastError());
+  });
+}
+
+int wcb_op_attention_decode_window(int dtype, const void* q, const void* k, const void* v, void* o, int B, int H, int Sq,
+                                   int Sk, const int32_t* key_start, int variant, void* stream) {
+  return guarded(nullptr, [&] {
+    const int kind = variant % 100, nsplit = variant >= 100 ? variant / 100 : 1;
+    REQUIRE(q && k && v && o && B > 0 && H > 0 && Sq > 0 && Sq <= Sk && Sk <= 2048, "bad argument");
+    REQUIRE(kind >= 0 && kind <= 7 && nsplit >= 1 && nsplit <= 64, "variant: 0..5 (+ 100·chunks), 6 or 7");
+    REQUIRE(kind < 6 || (Sq == 1 && nsplit == 1), "variants 6 and 7 are the one-token kernels (Sq = 1, no split)");
+    AttnArgs a;   // the runtime's self-attention call: q/o [B][Sq][H·64], K/V head-major [B][H][Sk][64]
+    a.q = q; a.ldq = (long)H * 64; a.q_Sb = Sq; a.Sq = Sq; a.causal = Sq > 1;
+    a.k = k; a.v = v; a.k_sb = (long)H * Sk * 64; a.k_sh = (long)Sk * 64; a.k_sk = 64;
+    a.o = o; a.ldo = (long)H * 64; a.o_Sb = Sq; a.B = B; a.H = H; a.nkeys = Sk - Sq + 1;
+    a.variant = kind; a.key_start = key_start;   // (null: the same launch on the dense kernels)
+    if (kind >= 6) a.kv_rows = Sk;
+    int* nk_dev = nullptr;
+    if (kind == 7) {   // the key count read on the device: the lean kernel (wcb_op_attention_decode's variant 7)
+      HIPCHK(hipMallocAsync(reinterpret_cast<void**>(&nk_dev), 4, (hipStream_t)stream));
+      const int nk1 = Sk - 1;
+      write_i32(nk_dev, &nk1, 1, (hipStream_t)stream);
+      a.nkeys_dev = nk_dev; a.nkeys_add = 1;
+    }
+    static DevBuf part, ticket;   // split-KV workspace of this test entry point (zeroed on growth)
+    if (nsplit > 1) {
+      a.nsplit = nsplit;
+      part.ensure((size_t)B * H * Sq * nsplit * 66 * 4);
+      ticket.ensure((size_t)B * H * Sq * 4);
       a.part = part.as<float>();
       a.ticket = ticket.as<int>();
     }

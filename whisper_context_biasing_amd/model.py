@@ -31,6 +31,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import prompts as _prompts
 from .config import (FRAME_SECONDS, N_SAMPLES, TIME_PRECISION, WhisperDims, dims_from_hf_config, get_dims, parse_segments,
                      timestamp_ids, words_from_token_times)
 
@@ -103,6 +104,19 @@ class GenerateOutput:
     # the model has a word_start mask: per clip a list of (start_s, end_s, token_ids) (config.words_from_token_times)
     token_timestamps: Optional[torch.Tensor] = None
     words: Optional[list] = None
+    # generate(prompt_ids=[[...], ...]) (per-clip prompts): prompt_lengths [B] int64, P_b = len(prompt b) + 1; sequences
+    # is then [B, Pmax + n], clip b's prompt left-padded with pad_token_id to Pmax = max P_b (prompts.unpack_prompts)
+    prompt_lengths: Optional[torch.Tensor] = None
+
+
+class _PackedPrompts:
+    """Per-clip prompts in the library's left-padded layout (prompts.pack_prompts): rows int32 [B, Pmax], lengths [B]."""
+
+    def __init__(self, rows: np.ndarray, lengths: np.ndarray):
+        self.rows, self.lengths = np.ascontiguousarray(rows), np.ascontiguousarray(lengths)
+
+    def __len__(self) -> int:   # the prompt width Pmax: what a flat prefix's length is to the length cap
+        return int(self.rows.shape[1])
 
 
 @dataclass
@@ -638,9 +652,33 @@ class WhisperCB:
         on the device). It works with every decode mode above and changes none of them. `num_frames` = mel frames of
         every clip ([B] ints, default 3000) crops the alignment to each clip's audio. With a `word_start` mask set the
         result also holds `words`.
+
+        `prompt_ids` = one flat prompt for every clip, or a sequence of B prompts, one per clip, of any lengths (an
+        empty one: no prompt; wcb_generate_prompted, greedy family only). Clip b then decodes exactly as it decodes
+        alone with `prompt_ids=prompt_ids[b]`. With `return_dict_in_generate` (or anything implying it) `sequences` is
+        [B, Pmax + n]: clip b's prompt and the start token left-padded with `pad_token_id` to Pmax = the longest
+        prompt + 1, so every clip's start token is column Pmax - 1 and the generated tokens follow in the same columns
+        (HF's layout for batched decoder prompts); `prompt_lengths` [B] = len(prompt b) + 1
+        (`prompts.unpack_prompts(sequences, prompt_lengths)` gives the prompts back). `token_logprobs`, `segments` and
+        `temperatures` stay aligned with the generated columns. The length cap is the widest prompt's: at most
+        `n_text_ctx - Pmax` new tokens. It works with bias lists, log-probs, sampling and the temperature fallback (a
+        failing clip is re-decoded with its own prompt), token rules, `use_graph` both ways, `block=False` and above 64
+        clips. Raises ValueError with `num_beams > 1` (beam scores count the prompt), with
+        `return_token_timestamps=True` (the alignment pass takes one shared prefix), and when the number of prompts
+        is not the number of clips.
         """
         if not self._loaded:
             raise _lib.WcbError("weights not loaded")
+        ragged = _prompts.is_nested(prompt_ids)
+        if ragged:   # per-clip prompts: greedy family only, and the alignment post-pass takes one shared prefix
+            if return_token_timestamps:
+                raise ValueError("return_token_timestamps with per-clip prompts is not supported (the alignment pass "
+                                 "takes one shared prefix)")
+            nb_rag = int(num_beams if num_beams is not None else getattr(generation_config or self.generation_config,
+                                                                          "num_beams", 1) or 1)
+            if nb_rag != 1:
+                raise ValueError("per-clip prompts are greedy only: num_beams must be 1 (beam scores count the prompt)")
+            prompt_ids = _prompts.as_lists(prompt_ids)
         if return_token_timestamps:
             if not block:
                 raise ValueError("return_token_timestamps reads the ids of the finished decode: block=False is not supported")
@@ -676,6 +714,8 @@ class WhisperCB:
             if return_timestamps and not block:
                 raise ValueError("return_timestamps parses the ids on the host: block=False is not supported")
         x_all = self._features(input_features)
+        if ragged and len(prompt_ids) != x_all.shape[0]:
+            raise ValueError(f"prompt_ids holds {len(prompt_ids)} prompts, the batch {x_all.shape[0]} clips")
         if isinstance(temperature, (list, tuple, np.ndarray)):
             if not block:
                 raise ValueError("temperature fallback reads every attempt's scores: block=False is not supported")
@@ -723,12 +763,20 @@ class WhisperCB:
                 kw["temperature"] = T
             parts = [self.generate(x_all[i:i + per_call],
                                    bias_lists=bias_lists[i:i + per_call] if bias_lists is not None else None,
-                                   **(dict(kw, seed=seeds[i:i + per_call]) if seeds is not None else kw))
+                                   **dict(kw, **(dict(seed=seeds[i:i + per_call]) if seeds is not None else {}),
+                                          **(dict(prompt_ids=prompt_ids[i:i + per_call]) if ragged else {})))
                      for i in range(0, x_all.shape[0], per_call)]
             seqs = [p.sequences if return_dict_in_generate else p for p in parts]
+            pl = None
+            if ragged and return_dict_in_generate:   # every part at its own prompt width: joined at the batch's
+                seqs = [p.sequences[:, int(p.prompt_lengths.max()):] for p in parts]
+                pl = torch.cat([p.prompt_lengths for p in parts])
             Wd = max(t.shape[1] for t in seqs)
             fill = self.dims.pad_token_id
             out = torch.cat([torch.nn.functional.pad(t, (0, Wd - t.shape[1]), value=fill) for t in seqs])
+            if pl is not None:
+                rows, _ = _prompts.pack_prompts(prompt_ids, self.dims.decoder_start_token_id, fill)
+                out = torch.cat([torch.from_numpy(rows.astype(np.int64)).to(out.device), out], dim=1)
             if output_logprobs:   # the parts' scores joined; log-prob columns past a part's width are 0
                 def join(name, width=None):
                     vals = [getattr(p, name) for p in parts]
@@ -740,10 +788,11 @@ class WhisperCB:
                 lp_w = max((p.token_logprobs.shape[1] for p in parts if p.token_logprobs is not None), default=0)
                 return GenerateOutput(sequences=out, token_logprobs=join("token_logprobs", lp_w),
                                       avg_logprob=join("avg_logprob"), sequences_scores=join("sequences_scores"),
-                                      segments=[s for p in parts for s in p.segments] if return_timestamps else None)
+                                      segments=[s for p in parts for s in p.segments] if return_timestamps else None,
+                                      prompt_lengths=pl)
             if return_timestamps:
-                return GenerateOutput(sequences=out, segments=[s for p in parts for s in p.segments])
-            return GenerateOutput(sequences=out) if return_dict_in_generate else out
+                return GenerateOutput(sequences=out, segments=[s for p in parts for s in p.segments], prompt_lengths=pl)
+            return GenerateOutput(sequences=out, prompt_lengths=pl) if return_dict_in_generate else out
         gc = generation_config or self.generation_config
         max_length = int(max_length if max_length is not None else getattr(gc, "max_length", 448))
         num_beams = int(num_beams if num_beams is not None else getattr(gc, "num_beams", 1) or 1)
@@ -751,7 +800,9 @@ class WhisperCB:
             raise ValueError("num_beams must be in [1, 8]")
         x = x_all
         prefix = [self.dims.decoder_start_token_id]
-        if prompt_ids is not None:
+        if ragged:   # the left-padded rows [B, Pmax] and the lengths (the batch's length cap is the widest prompt's)
+            prefix = _PackedPrompts(*_prompts.pack_prompts(prompt_ids, self.dims.decoder_start_token_id, self.dims.pad_token_id))
+        elif prompt_ids is not None:
             prefix = [int(t) for t in prompt_ids] + prefix
         # HF: max_length + prompt tokens, capped at max_target_positions ([tf] generation_whisper.py:1932-1940)
         max_new = min(max_length, self.dims.n_text_ctx - len(prefix))
@@ -781,14 +832,19 @@ class WhisperCB:
         lp = torch.zeros(B, max_new, dtype=torch.float32, device=self.device) if scored and not beams else None
         ss = torch.zeros(B, dtype=torch.float32, device=self.device) if scored and beams else None
         steps = C.c_int32(0)
-        pre = np.asarray(prefix, dtype=np.int32)
+        packed = isinstance(prefix, _PackedPrompts)
+        pre = None if packed else np.asarray(prefix, dtype=np.int32)
         bb = BiasBatch(self, bias_lists) if bias_lists is not None else None   # per call: not in the automaton LRU
         head = (self._h, _ptr(x), B, C.byref(cfg))
         bias = (bl._h if (bl and not bb) else None, bb._h if bb else None)
-        mid = (pre.ctypes.data if len(prefix) > 1 else None, len(prefix), _ptr(out))
+        mid = None if packed else (pre.ctypes.data if len(prefix) > 1 else None, len(prefix), _ptr(out))
         scores = (_ptr(lp) if lp is not None else None, _ptr(ss) if ss is not None else None)
         tail = (C.byref(steps), _stream(self.device))
-        if smp is not None:
+        if packed:   # per-clip prompts: the greedy family in one entry point
+            name = "wcb_generate_prompted"
+            args = head + (C.byref(smp) if smp is not None else None,) + bias + (
+                prefix.rows.ctypes.data, prefix.rows.shape[1], prefix.lengths.ctypes.data, _ptr(out)) + scores[:1] + tail
+        elif smp is not None:
             name, args = "wcb_generate_sampled", head + (C.byref(smp),) + bias + mid + scores[:1] + tail
         elif scored:
             name, args = "wcb_generate_scored", head + bias + mid + scores + tail
@@ -814,9 +870,14 @@ class WhisperCB:
         if not as_dict:
             return self._whisper_trim(ids)
         B = ids.shape[0]
-        sot = torch.tensor(prefix, dtype=torch.int64, device=self.device)[None].expand(B, -1)
+        if isinstance(prefix, _PackedPrompts):
+            sot = torch.from_numpy(prefix.rows.astype(np.int64)).to(self.device)
+        else:
+            sot = torch.tensor(prefix, dtype=torch.int64, device=self.device)[None].expand(B, -1)
         res = GenerateOutput(sequences=torch.cat([sot, ids], dim=1), sequences_scores=ss,
                              segments=self._segments(ids.cpu().numpy()) if timestamps else None)
+        if isinstance(prefix, _PackedPrompts):
+            res.prompt_lengths = torch.from_numpy(prefix.lengths.astype(np.int64)).to(self.device)
         if lp is not None:
             res.token_logprobs = lp[:, :n]
             # Whisper's avg_logprob on the host: each row's tokens up to and including its EOS (a finished row's
@@ -858,7 +919,9 @@ class WhisperCB:
         seqs, lps = [None] * B, [None] * B
         avg, used = np.zeros(B, dtype=np.float32), np.zeros(B, dtype=np.float32)
         todo = np.arange(B)
-        P = 1 + (len(kw["prompt_ids"]) if kw["prompt_ids"] is not None else 0)
+        prompts_all = kw.pop("prompt_ids")
+        ragged = _prompts.is_nested(prompts_all)   # per-clip prompts: a failing clip is re-decoded with its own
+        P = 1 + (len(prompts_all) if prompts_all is not None and not ragged else 0)
         for i, T in enumerate(temps):
             if explicit is not None:
                 sd = np.asarray([(explicit[b] + i * 0x9E3779B97F4A7C15) & _M64 for b in todo], dtype=np.uint64)
@@ -867,7 +930,9 @@ class WhisperCB:
             idx = torch.as_tensor(todo, device=x_all.device)
             res = self.generate(x_all[idx] if len(todo) < B else x_all, temperature=T, seed=sd, output_logprobs=True,
                                 bias_list=bias_list, bias_lists=[bias_lists[b] for b in todo] if bias_lists is not None else None,
-                                **kw)
+                                prompt_ids=[prompts_all[b] for b in todo] if ragged else prompts_all, **kw)
+            if ragged:
+                P = int(res.prompt_lengths.max())   # this attempt's own prompt width
             ids_h = res.sequences[:, P:].cpu().numpy()
             lp_h = res.token_logprobs.cpu().numpy()
             avg_h = res.avg_logprob.cpu().numpy()
@@ -889,12 +954,17 @@ class WhisperCB:
         for b in range(B):
             ids[b, :len(seqs[b])] = seqs[b]
             lp[b, :len(lps[b])] = lps[b]
-        prefix = ([int(t) for t in kw["prompt_ids"]] if kw["prompt_ids"] is not None else []) + [self.dims.decoder_start_token_id]
-        sot = np.broadcast_to(np.asarray(prefix, dtype=np.int64), (B, len(prefix)))
         dev = self.device
+        plen = None
+        if ragged:
+            sot, plen = _prompts.pack_prompts(prompts_all, self.dims.decoder_start_token_id, self.dims.pad_token_id)
+            sot, plen = sot.astype(np.int64), torch.from_numpy(plen.astype(np.int64)).to(dev)
+        else:
+            prefix = ([int(t) for t in prompts_all] if prompts_all is not None else []) + [self.dims.decoder_start_token_id]
+            sot = np.broadcast_to(np.asarray(prefix, dtype=np.int64), (B, len(prefix)))
         return GenerateOutput(sequences=torch.from_numpy(np.concatenate([sot, ids], axis=1)).to(dev),
                               token_logprobs=torch.from_numpy(lp).to(dev), avg_logprob=torch.from_numpy(avg).to(dev),
-                              temperatures=torch.from_numpy(used).to(dev))
+                              temperatures=torch.from_numpy(used).to(dev), prompt_lengths=plen)
 
     def decode_begin(self, encoder_outputs, prompt_ids=None, bias_list=None, bias_boost: float = 0.0,
                      min_new_tokens: int = 0, num_beams: int = 1, max_length: Optional[int] = None,
@@ -904,8 +974,11 @@ class WhisperCB:
         """Step-wise decoding from an encoder output [B, 1500, d] (this model's dtype, on its device): the
         streaming form of generate() (wcb_decode_begin / wcb_decode_begin_beams). Greedy (num_beams = 1) or
         beam search (num_beams 2..8; `max_length` = generate()'s, the beams' length cap: None = the
-        max_target_positions cap). `prompt_ids` = one prompt for every clip or a [B, P] array of per-clip
-        prompts (decoder_start_token_id is appended as generate() does). `bias_lists` = per-clip phrase lists as
+        max_target_positions cap). `prompt_ids` = one prompt for every clip, a [B, P] array of per-clip
+        prompts, or a list of B prompts of different lengths (empty: none; wcb_decode_begin_prompted, greedy only:
+        ValueError with num_beams > 1 or when its length is not B) — decoder_start_token_id is appended as
+        generate() does, every clip decodes as it does alone with its prompt, and step() / result() / logprobs()
+        return the generated tokens as for any decode. `bias_lists` = per-clip phrase lists as
         generate() takes them (wcb_decode_bias_batch; a shared `bias_list` of phrases is appended to each).
         `logprobs=True` (greedy): StepDecoder.logprobs() gives the token log-probs of the steps taken.
         `temperature > 0` (greedy): every step samples as generate(temperature=..., seed=...) does
@@ -937,7 +1010,17 @@ class WhisperCB:
                 if seeds.shape[0] != B:
                     raise ValueError(f"seed has {seeds.shape[0]} entries, the batch {B} clips")
         start = self.dims.decoder_start_token_id
-        if prompt_ids is None:
+        packed = None
+        if _prompts.is_nested(prompt_ids) and not isinstance(prompt_ids, np.ndarray):
+            plists = _prompts.as_lists(prompt_ids)
+            if len(plists) != B:
+                raise ValueError(f"prompt_ids holds {len(plists)} prompts, the batch {B} clips")
+            if len({len(p) for p in plists}) > 1:   # ragged: the left-padded form (equal lengths: the [B, P] path)
+                if int(num_beams) != 1:
+                    raise ValueError("per-clip prompts of different lengths are greedy only: num_beams must be 1")
+                packed = _PackedPrompts(*_prompts.pack_prompts(plists, start, self.dims.pad_token_id))
+            prompt_ids = plists
+        if prompt_ids is None or packed is not None:
             pre = None
         else:
             p = np.asarray(prompt_ids, dtype=np.int32)
@@ -955,7 +1038,12 @@ class WhisperCB:
         st = C.c_void_p()
         nb = int(num_beams)
         self._install_rules(rules)
-        if nb > 1 and max_length is not None:
+        if packed is not None:
+            _lib.check(self._lib.wcb_decode_begin_prompted(self._h, _ptr(enc), B, packed.rows.ctypes.data, packed.rows.shape[1],
+                                                           packed.lengths.ctypes.data, float(bias_boost), int(min_new_tokens),
+                                                           C.byref(st), _stream(self.device)), self._h,
+                       "wcb_decode_begin_prompted")
+        elif nb > 1 and max_length is not None:
             _lib.check(self._lib.wcb_decode_begin_beams(self._h, _ptr(enc), B, nb, pre.ctypes.data if pre is not None else None,
                                                         pre.shape[1] if pre is not None else 1, int(max_length),
                                                         float(bias_boost), int(min_new_tokens), C.byref(st),
