@@ -12,6 +12,7 @@ compared when the reference's top-two gap exceeds 1e-4·max(1, |x_top|) and coun
 share is bounded (1 % of the op rows, one row of the step-wise test).
 """
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
@@ -340,6 +341,18 @@ def test_more_than_64_sampled_clips_split_invisibly():
 
 
 # ------------------------------------------------------------------------------------------------------ 8. fallback
+def same_rows(m, out, rows, ref, ref_rows=None):
+    """rows of `out` equal rows of `ref` up to the padding of the joined output"""
+    ref_rows = rows if ref_rows is None else ref_rows
+    w = min(out.sequences.shape[1], ref.sequences.shape[1])
+    wl = min(out.token_logprobs.shape[1], ref.token_logprobs.shape[1])
+    pad = m.dims.pad_token_id
+    return (torch.equal(out.sequences[rows, :w], ref.sequences[ref_rows, :w]) and
+            bool((out.sequences[rows, w:] == pad).all()) and bool((ref.sequences[ref_rows, w:] == pad).all()) and
+            torch.equal(out.token_logprobs[rows, :wl], ref.token_logprobs[ref_rows, :wl]) and
+            bool((out.token_logprobs[rows, wl:] == 0).all()) and bool((ref.token_logprobs[ref_rows, wl:] == 0).all()))
+
+
 def test_temperature_fallback():
     m = model("f32")
     x = mel_batch(4).to(m.device)
@@ -349,17 +362,7 @@ def test_temperature_fallback():
     order = np.argsort(avg)
     print(f"fallback: greedy avg_logprob {avg}")
     assert len(set(avg.tolist())) == 4
-
-    def same(out, rows, ref, ref_rows=None):
-        """rows of `out` equal rows of `ref` up to the padding of the joined output"""
-        ref_rows = rows if ref_rows is None else ref_rows
-        w = min(out.sequences.shape[1], ref.sequences.shape[1])
-        wl = min(out.token_logprobs.shape[1], ref.token_logprobs.shape[1])
-        pad = m.dims.pad_token_id
-        return (torch.equal(out.sequences[rows, :w], ref.sequences[ref_rows, :w]) and
-                bool((out.sequences[rows, w:] == pad).all()) and bool((ref.sequences[ref_rows, w:] == pad).all()) and
-                torch.equal(out.token_logprobs[rows, :wl], ref.token_logprobs[ref_rows, :wl]) and
-                bool((out.token_logprobs[rows, wl:] == 0).all()) and bool((ref.token_logprobs[ref_rows, wl:] == 0).all()))
+    same = functools.partial(same_rows, m)
 
     # every clip passes at T = 0
     out = m.generate(x, temperature=(0.0, 0.5, 1.0), logprob_threshold=-np.inf, **kw)
@@ -398,6 +401,46 @@ def test_temperature_fallback():
                      bias_lists=lists, bias_boost=50.0, **kw)
     assert out.temperatures.cpu().numpy().tolist() == [1.0, 0.0, 0.0, 0.0]
     assert same(out, [1, 2, 3], forced)
+
+
+# The clips of mel_batch(70)[:66] in the order test_temperature_fallback_above_64_clips decodes them. As generated, the
+# widest gap of the greedy avg_logprob has clips 19, 41, 43, 48 and 52 below it, all in the first 64; clip 41 changes
+# places with clip 64, so that the second library call of the split holds a failing and a passing clip too.
+ORDER_66 = list(range(66))
+ORDER_66[41], ORDER_66[64] = 64, 41
+
+
+def test_temperature_fallback_above_64_clips():
+    """66 clips, so every attempt is split at 64 clips, and a threshold that fails some clips of both parts: the
+    failing clips of the whole batch decode again together, each with the seed of its place in the whole batch."""
+    m = model("f32")
+    x = mel_batch(70)[:66][ORDER_66]
+    seed = 77
+    greedy = m.generate(x, max_length=6, output_logprobs=True)
+    avg = greedy.avg_logprob.cpu().numpy().astype(np.float64)
+    s = np.sort(avg)
+    gaps = s[3:64] - s[2:63]   # gaps[k - 3] = s[k] - s[k - 1]: k clips fail, 66 - k pass, k = 3 .. 63
+    k = 3 + int(np.argmax(gaps))
+    thr = float(s[k - 1] + s[k]) / 2
+    fail = avg < thr
+    print(f"fallback above 64 clips: {k} clips fail, gap {gaps.max():.3e}, failing {np.flatnonzero(fail).tolist()}, "
+          f"order by avg_logprob {np.argsort(avg).tolist()}")
+    assert gaps.max() > 1e-3   # the f32 margin of test_temperature_fallback's thresholds
+    assert int(fail.sum()) == k
+    for part in (fail[:64], fail[64:]):   # both library calls of the split hold a failing and a passing clip
+        assert part.any() and not part.all(), fail
+    out = m.generate(x, max_length=6, temperature=(0.0, 0.7), seed=seed, logprob_threshold=thr,
+                     compression_ratio_threshold=None)
+    temps = out.temperatures.cpu().numpy()
+    assert np.array_equal(temps, np.where(fail, np.float32(0.7), np.float32(0.0))), temps
+    passing = np.flatnonzero(~fail).tolist()
+    assert same_rows(m, out, passing, greedy)
+    assert torch.equal(out.avg_logprob[passing], greedy.avg_logprob[passing])
+    seeds = clip_seeds(seed, 0, 66, attempt=1)
+    for b in np.flatnonzero(fail).tolist():
+        solo = m.generate(x[b:b + 1], max_length=6, temperature=0.7, seed=[int(seeds[b])], output_logprobs=True)
+        assert same_rows(m, out, [b], solo, [0]), b
+        assert torch.equal(out.avg_logprob[b:b + 1], solo.avg_logprob), b
 
 
 # -------------------------------------------------------------------------------------------------------- 9. errors

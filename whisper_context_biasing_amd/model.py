@@ -20,10 +20,8 @@ memory and streams. There is no CPU fallback.
 from __future__ import annotations
 
 import ctypes as C
-import math
-import zlib
 from collections import OrderedDict
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from types import SimpleNamespace
 from typing import Dict, List, Optional, Sequence
 
@@ -32,8 +30,10 @@ import torch
 
 from . import _lib
 from . import prompts as _prompts
-from .config import (FRAME_SECONDS, N_SAMPLES, TIME_PRECISION, WhisperDims, dims_from_hf_config, get_dims, parse_segments,
-                     timestamp_ids, words_from_token_times)
+from . import request as _request
+from .config import (FRAME_SECONDS, N_SAMPLES, WhisperDims, dims_from_hf_config, get_dims, parse_segments, timestamp_ids,
+                     words_from_token_times)
+from .request import DecodeRequest, _mix64, clip_seeds, compression_ratio  # noqa: F401  (importable from here, as ever)
 
 _TORCH_DT = {_lib.WCB_BF16: torch.bfloat16, _lib.WCB_F16: torch.float16, _lib.WCB_F32: torch.float32}
 
@@ -44,44 +44,6 @@ def _ptr(t: torch.Tensor) -> int:
 
 def _stream(device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
-
-
-_M64 = (1 << 64) - 1
-
-
-def _mix64(z: int) -> int:
-    """splitmix64's finaliser: a bijection of the 64-bit integers."""
-    z &= _M64
-    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
-    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
-    return z ^ (z >> 31)
-
-
-def clip_seeds(seed: int, first_clip: int, n: int, attempt: int = 0) -> np.ndarray:
-    """The per-clip 64-bit sampling seeds an int `seed` stands for: clip c (its index in the WHOLE batch) of
-    fallback attempt a draws with  mix64(mix64(seed) + (a << 32 | c))  (mix64 = splitmix64's finaliser, sums
-    mod 2^64). Returns the seeds of clips first_clip .. first_clip + n - 1 as uint64 [n]. A pure function:
-    mix64 is a bijection, so distinct (clip < 2^32, attempt < 2^32) give distinct seeds, a batch split anywhere
-    gives the values of the unsplit batch, and every attempt draws fresh noise."""
-    if not (0 <= int(first_clip) and int(first_clip) + int(n) <= 1 << 32 and 0 <= int(attempt) < 1 << 32):
-        raise ValueError("clip_seeds: clip indices and attempt must fit 32 bits")
-    base = _mix64(int(seed))
-    return np.asarray([_mix64(base + ((int(attempt) << 32) | c)) for c in range(int(first_clip), int(first_clip) + int(n))],
-                      dtype=np.uint64)
-
-
-def compression_ratio(ids, vocab: int, eos: Optional[int] = None) -> float:
-    """HF's `_retrieve_compression_ratio` ([tf] generation_whisper.py) of one clip's tokens: those before the
-    first `eos` (all of them when eos is None or absent), each written as int(log2(vocab) / 8) + 1 little-endian
-    bytes; len(bytes) / len(zlib.compress(bytes)). No tokens: 0.0."""
-    toks = [int(t) for t in np.asarray(ids).reshape(-1)]
-    if eos is not None and int(eos) in toks:
-        toks = toks[:toks.index(int(eos))]
-    if not toks:
-        return 0.0
-    length = int(math.log2(vocab) / 8) + 1
-    data = b"".join(t.to_bytes(length, "little") for t in toks)
-    return len(data) / len(zlib.compress(data))
 
 
 @dataclass
@@ -491,81 +453,7 @@ class WhisperCB:
             self._bias_cache.move_to_end(key)
         return b
 
-    # the reference collator pads bias_spans with the literal 50256 whatever the model
-    # (data_utils/data_collator.py:119-121)
-    collator_span_pad = 50256
-
-    def _spans_to_phrases(self, bias_spans) -> List[List[int]]:
-        """Union of the collator's padded per-sample spans ([B, N, L], pad 50256 —
-        data_utils/data_collator.py:107-125; the all-zeros [B, 1, 1] "no spans" form gives none) with
-        the padding stripped."""
-        pad = self.collator_span_pad
-        arr = torch.as_tensor(bias_spans).cpu().numpy()
-        out, seen = [], set()
-        for sample in arr:
-            for span in sample:
-                toks = tuple(int(t) for t in span if int(t) != pad)
-                if toks and any(toks) and toks not in seen:
-                    seen.add(toks)
-                    out.append(list(toks))
-        return out
-
-    def _spans_to_lists(self, bias_spans) -> List[List[List[int]]]:
-        """The collator tensor per sample (per_utterance_bias=True): row b's spans with the padding stripped
-        are clip b's list; the all-zeros [B, 1, 1] form gives empty lists."""
-        pad = self.collator_span_pad
-        arr = torch.as_tensor(bias_spans).cpu().numpy()
-        out = []
-        for sample in arr:
-            L, seen = [], set()
-            for span in sample:
-                toks = tuple(int(t) for t in span if int(t) != pad)
-                if toks and any(toks) and toks not in seen:
-                    seen.add(toks)
-                    L.append(list(toks))
-            out.append(L)
-        return out
-
-    def _clip_lists(self, bias_lists, bias_list, B: int) -> List[List[List[int]]]:
-        """bias_lists checked against the batch, a shared bias_list (phrases, not a prebuilt automaton)
-        concatenated into every clip's list."""
-        lists = [[list(map(int, p)) for p in L] for L in bias_lists]
-        if len(lists) != B:
-            raise ValueError(f"bias_lists has {len(lists)} lists, the batch {B} clips")
-        if bias_list is not None:
-            if isinstance(bias_list, BiasList):
-                raise ValueError("bias_lists takes a shared bias_list as phrases, not as a prebuilt BiasList")
-            shared = [list(map(int, p)) for p in bias_list]
-            lists = [L + shared for L in lists]
-        return lists
-
     # ---------------------------------------------------------------------------- generation
-    def _rules_key_of(self, return_timestamps, suppress_tokens, begin_suppress_tokens, max_initial_timestamp):
-        """The token rules the four generate() / decode_begin() arguments ask for, as a hashable key (None: none)."""
-        sup = tuple(sorted({int(t) for t in (suppress_tokens or ())}))
-        beg = tuple(sorted({int(t) for t in (begin_suppress_tokens or ())}))
-        ts = bool(return_timestamps)
-        for t in sup + beg:
-            if not 0 <= t < self.dims.vocab:
-                raise ValueError(f"suppress id {t} outside [0, {self.dims.vocab})")
-        mi = -1
-        if max_initial_timestamp is not None:
-            if not ts:
-                raise ValueError("max_initial_timestamp needs return_timestamps=True")
-            if not (float(max_initial_timestamp) >= 0.0 and math.isfinite(float(max_initial_timestamp))):
-                raise ValueError(f"max_initial_timestamp must be finite and >= 0, got {max_initial_timestamp!r}")
-            mi = int(round(float(max_initial_timestamp) / TIME_PRECISION))
-        if not (ts or sup or beg):
-            return None
-        if ts:
-            ts0 = timestamp_ids(self.dims)[0]
-            if ts0 <= self.dims.eos_token_id:
-                raise ValueError("this vocabulary has no timestamp tokens past EOS")
-            bad = [t for t in sup + beg if t >= ts0]
-            if bad:
-                raise ValueError(f"suppress ids {bad} are timestamp tokens (>= {ts0}): the grammar decides those")
-        return (sup, beg, ts, mi)
-
     def _install_rules(self, key) -> None:
         """Make `key` the handle's token rules (handle state, like a generation config; a no-op when it already is)."""
         if key == self._rules_key:
@@ -669,164 +557,62 @@ class WhisperCB:
         """
         if not self._loaded:
             raise _lib.WcbError("weights not loaded")
-        ragged = _prompts.is_nested(prompt_ids)
-        if ragged:   # per-clip prompts: greedy family only, and the alignment post-pass takes one shared prefix
-            if return_token_timestamps:
-                raise ValueError("return_token_timestamps with per-clip prompts is not supported (the alignment pass "
-                                 "takes one shared prefix)")
-            nb_rag = int(num_beams if num_beams is not None else getattr(generation_config or self.generation_config,
-                                                                          "num_beams", 1) or 1)
-            if nb_rag != 1:
-                raise ValueError("per-clip prompts are greedy only: num_beams must be 1 (beam scores count the prompt)")
-            prompt_ids = _prompts.as_lists(prompt_ids)
-        if return_token_timestamps:
-            if not block:
-                raise ValueError("return_token_timestamps reads the ids of the finished decode: block=False is not supported")
-            input_features = self._features(input_features)
-            B_all = int(input_features.shape[0])
-            akw = self._align_args(B_all, alignment_heads, num_frames, median_filter_width)   # ValueError before any work
-            res = self.generate(input_features, labels=labels, bias_spans=bias_spans, max_length=max_length,
-                                num_beams=num_beams, bias_list=bias_list, bias_boost=bias_boost,
-                                min_new_tokens=min_new_tokens, prompt_ids=prompt_ids, return_dict_in_generate=True,
-                                generation_config=generation_config, use_graph=use_graph, block=True,
-                                bias_lists=bias_lists, per_utterance_bias=per_utterance_bias,
-                                output_logprobs=output_logprobs, temperature=temperature, seed=seed, do_sample=do_sample,
-                                logprob_threshold=logprob_threshold,
-                                compression_ratio_threshold=compression_ratio_threshold,
-                                return_timestamps=return_timestamps, suppress_tokens=suppress_tokens,
-                                begin_suppress_tokens=begin_suppress_tokens,
-                                max_initial_timestamp=max_initial_timestamp, **kwargs)
-            P = 1 + (len(prompt_ids) if prompt_ids is not None else 0)
-            return self._attach_token_timestamps(res, input_features, P, akw)
-        if output_logprobs or return_timestamps:
-            return_dict_in_generate = True
-        rules_kw = dict(return_timestamps=return_timestamps, suppress_tokens=suppress_tokens,
-                        begin_suppress_tokens=begin_suppress_tokens, max_initial_timestamp=max_initial_timestamp)
-        rules = self._rules_key_of(**rules_kw)
-        if rules is not None:   # what the library refuses, before any work
-            nb_rules = int(num_beams if num_beams is not None else getattr(generation_config or self.generation_config,
-                                                                            "num_beams", 1) or 1)
-            if nb_rules != 1:
-                raise ValueError("suppress_tokens / begin_suppress_tokens / return_timestamps are greedy only: num_beams must be 1")
-            if return_timestamps and (isinstance(temperature, (list, tuple, np.ndarray)) or do_sample
-                                      or (do_sample is not False and float(temperature) > 0.0)):
-                raise ValueError("return_timestamps with sampling or a temperature fallback is not supported")
-            if return_timestamps and not block:
-                raise ValueError("return_timestamps parses the ids on the host: block=False is not supported")
-        x_all = self._features(input_features)
-        if ragged and len(prompt_ids) != x_all.shape[0]:
-            raise ValueError(f"prompt_ids holds {len(prompt_ids)} prompts, the batch {x_all.shape[0]} clips")
-        if isinstance(temperature, (list, tuple, np.ndarray)):
-            if not block:
-                raise ValueError("temperature fallback reads every attempt's scores: block=False is not supported")
-            return self._generate_with_fallback(
-                x_all, [float(t) for t in temperature], seed, logprob_threshold, compression_ratio_threshold,
-                dict(labels=labels, bias_spans=bias_spans, max_length=max_length, num_beams=num_beams, bias_list=bias_list,
-                     bias_boost=bias_boost, min_new_tokens=min_new_tokens, prompt_ids=prompt_ids,
-                     generation_config=generation_config, use_graph=use_graph, bias_lists=bias_lists,
-                     per_utterance_bias=per_utterance_bias, **rules_kw))
-        T = float(temperature)
-        if do_sample and T == 0.0:
-            T = 1.0
-        if do_sample is False:
-            T = 0.0
-        if not (T >= 0.0 and math.isfinite(T)):
-            raise ValueError(f"temperature must be finite and >= 0, got {temperature!r}")
-        seeds = None   # uint64 [B] of the whole batch when sampling
-        if T > 0.0:
-            if isinstance(seed, (int, np.integer)):
-                seeds = clip_seeds(int(seed), 0, x_all.shape[0])
-            else:
-                seeds = np.ascontiguousarray(np.asarray([int(v) & _M64 for v in seed], dtype=np.uint64))
-                if seeds.shape[0] != x_all.shape[0]:
-                    raise ValueError(f"seed has {seeds.shape[0]} entries, the batch {x_all.shape[0]} clips")
-        if bias_lists is None and per_utterance_bias and bias_list is None and bias_boost > 0 and bias_spans is not None:
-            bias_lists = self._spans_to_lists(bias_spans)
-        if bias_lists is not None:   # checked on the whole batch, before any split
-            bias_lists, bias_list = self._clip_lists(bias_lists, bias_list, x_all.shape[0]), None
-        nb_req = int(num_beams if num_beams is not None else getattr(generation_config or self.generation_config,
-                                                                      "num_beams", 1) or 1)
-        if seeds is not None and nb_req != 1:
-            raise ValueError("sampling (temperature > 0) is greedy only: num_beams must be 1")
-        per_call = self.max_clips_per_call(nb_req)
-        if x_all.shape[0] > per_call:
-            # the library takes at most 64 clips (512 decoder rows) per call: split, decode in order,
-            # re-pad to the longest row (Whisper's padding of the joined output)
-            kw = dict(labels=labels, bias_spans=bias_spans, max_length=max_length, num_beams=num_beams,
-                      bias_list=bias_list, bias_boost=bias_boost, min_new_tokens=min_new_tokens,
-                      prompt_ids=prompt_ids, return_dict_in_generate=return_dict_in_generate,
-                      generation_config=generation_config, use_graph=use_graph, block=True,
-                      output_logprobs=output_logprobs, **rules_kw)
-            if bias_lists is None and bias_list is None and bias_boost > 0 and bias_spans is not None:
-                kw["bias_list"], kw["bias_spans"] = self._spans_to_phrases(bias_spans), None
-            if seeds is not None:
-                kw["temperature"] = T
-            parts = [self.generate(x_all[i:i + per_call],
-                                   bias_lists=bias_lists[i:i + per_call] if bias_lists is not None else None,
-                                   **dict(kw, **(dict(seed=seeds[i:i + per_call]) if seeds is not None else {}),
-                                          **(dict(prompt_ids=prompt_ids[i:i + per_call]) if ragged else {})))
-                     for i in range(0, x_all.shape[0], per_call)]
-            seqs = [p.sequences if return_dict_in_generate else p for p in parts]
-            pl = None
-            if ragged and return_dict_in_generate:   # every part at its own prompt width: joined at the batch's
-                seqs = [p.sequences[:, int(p.prompt_lengths.max()):] for p in parts]
-                pl = torch.cat([p.prompt_lengths for p in parts])
-            Wd = max(t.shape[1] for t in seqs)
-            fill = self.dims.pad_token_id
-            out = torch.cat([torch.nn.functional.pad(t, (0, Wd - t.shape[1]), value=fill) for t in seqs])
-            if pl is not None:
-                rows, _ = _prompts.pack_prompts(prompt_ids, self.dims.decoder_start_token_id, fill)
-                out = torch.cat([torch.from_numpy(rows.astype(np.int64)).to(out.device), out], dim=1)
-            if output_logprobs:   # the parts' scores joined; log-prob columns past a part's width are 0
-                def join(name, width=None):
-                    vals = [getattr(p, name) for p in parts]
-                    if any(v is None for v in vals):
-                        return None
-                    if width is not None:
-                        vals = [torch.nn.functional.pad(v, (0, width - v.shape[1])) for v in vals]
-                    return torch.cat(vals)
-                lp_w = max((p.token_logprobs.shape[1] for p in parts if p.token_logprobs is not None), default=0)
-                return GenerateOutput(sequences=out, token_logprobs=join("token_logprobs", lp_w),
-                                      avg_logprob=join("avg_logprob"), sequences_scores=join("sequences_scores"),
-                                      segments=[s for p in parts for s in p.segments] if return_timestamps else None,
-                                      prompt_lengths=pl)
-            if return_timestamps:
-                return GenerateOutput(sequences=out, segments=[s for p in parts for s in p.segments], prompt_lengths=pl)
-            return GenerateOutput(sequences=out, prompt_lengths=pl) if return_dict_in_generate else out
-        gc = generation_config or self.generation_config
-        max_length = int(max_length if max_length is not None else getattr(gc, "max_length", 448))
-        num_beams = int(num_beams if num_beams is not None else getattr(gc, "num_beams", 1) or 1)
-        if not 1 <= num_beams <= 8:
-            raise ValueError("num_beams must be in [1, 8]")
-        x = x_all
-        prefix = [self.dims.decoder_start_token_id]
-        if ragged:   # the left-padded rows [B, Pmax] and the lengths (the batch's length cap is the widest prompt's)
-            prefix = _PackedPrompts(*_prompts.pack_prompts(prompt_ids, self.dims.decoder_start_token_id, self.dims.pad_token_id))
-        elif prompt_ids is not None:
-            prefix = [int(t) for t in prompt_ids] + prefix
-        # HF: max_length + prompt tokens, capped at max_target_positions ([tf] generation_whisper.py:1932-1940)
-        max_new = min(max_length, self.dims.n_text_ctx - len(prefix))
-        if max_new < 1:
-            raise ValueError("prompt leaves no room for new tokens")
-        phrases = bias_list
-        if bias_lists is not None:
-            phrases = None
-        elif phrases is None and bias_boost > 0 and bias_spans is not None:
-            phrases = self._spans_to_phrases(bias_spans)
-        if isinstance(phrases, BiasList):          # a prebuilt automaton (it must belong to this model)
-            bl = phrases if bias_boost > 0 else None
-        else:
-            bl = self.bias_list(phrases) if (phrases and bias_boost > 0) else None
-        cfg = _lib.WcbGenCfg(max_new, int(min_new_tokens), num_beams, float(bias_boost), int(use_graph), int(not block))
-        smp = _lib.WcbSampleCfg(T, seeds.ctypes.data_as(C.POINTER(C.c_uint64))) if seeds is not None else None
-        self._install_rules(rules)
-        out, n, lp, ss = self._decode_call(x, cfg, bl, bias_lists if bias_boost > 0 else None, prefix, smp, output_logprobs)
-        return self._generate_result(out, n, prefix, block, return_dict_in_generate, lp, ss, return_timestamps)
+        x = torch.as_tensor(input_features)
+        req = _request.resolve(   # every ValueError of the arguments, before any device work
+            self.dims, generation_config or self.generation_config, int(x.shape[0]) if x.dim() > 2 else 1,
+            bias_spans=None if bias_spans is None else (lambda: torch.as_tensor(bias_spans).cpu().numpy()),
+            max_length=max_length, num_beams=num_beams, bias_list=bias_list, bias_boost=bias_boost, bias_lists=bias_lists,
+            per_utterance_bias=per_utterance_bias, min_new_tokens=min_new_tokens, prompt_ids=prompt_ids, use_graph=use_graph,
+            block=block, return_dict_in_generate=return_dict_in_generate, output_logprobs=output_logprobs, seed=seed,
+            temperature=temperature, do_sample=do_sample, logprob_threshold=logprob_threshold,
+            compression_ratio_threshold=compression_ratio_threshold, return_timestamps=return_timestamps,
+            suppress_tokens=suppress_tokens, begin_suppress_tokens=begin_suppress_tokens,
+            max_initial_timestamp=max_initial_timestamp, return_token_timestamps=return_token_timestamps,
+            alignment_heads=alignment_heads, num_frames=num_frames, median_filter_width=median_filter_width)
+        x = self._features(x)
+        res = self._generate_with_fallback(x, req) if req.temperatures is not None else self._decode(x, req)
+        if req.align is not None:   # right after the decode: one library call leaves its encoder state to the alignment
+            res = self._attach_token_timestamps(res, x, req.prompt_width, req.align)
+        return res
 
-    def _decode_call(self, x, cfg, bl, bias_lists, prefix, smp, scored):
-        """One library decode of the batch x: the shared automaton `bl`, the per-clip `bias_lists` (a BiasBatch that
-        lives for this call) or neither; `smp` samples; `scored` asks for token log-probs (greedy) or sequence scores
-        (beams). Returns (ids int32 [B, max_new], generated columns, log-probs or None, sequence scores or None)."""
+    def _decode(self, x, req: DecodeRequest):
+        """generate()'s result for the clips x of `req`: one library call, or — the library takes at most 64 clips
+        (512 decoder rows) per call — one per chunk in order, each blocking, on its own slice of the request, joined."""
+        per_call = self.max_clips_per_call(req.num_beams)
+        if req.B <= per_call:
+            return self._decode_call(x, req)
+        parts = []
+        for i in range(0, req.B, per_call):
+            sub = replace(req.take(range(i, min(i + per_call, req.B))), block=True)
+            parts.append((slice(i, i + sub.B), slice(None), self._decode_call(x[i:i + per_call], sub), sub.prompt_width))
+        return self._join(req, parts)
+
+    def _prefix(self, req: DecodeRequest):
+        """The decoder prompt of one library call: flat prompt + start token, or per-clip prompts packed at these clips' width."""
+        start = self.dims.decoder_start_token_id
+        if req.per_clip_prompts:
+            return _PackedPrompts(*_prompts.pack_prompts(req.prompt, start, self.dims.pad_token_id))
+        return list(req.prompt or []) + [start]
+
+    def _automaton(self, shared, bias_boost: float) -> Optional[BiasList]:
+        """A shared bias source's automaton: a prebuilt BiasList (this model's) as it is, phrases through the LRU, or None."""
+        if shared is None or not bias_boost > 0:
+            return None
+        if _request.is_prebuilt(shared):
+            return shared
+        return self.bias_list(shared) if shared else None
+
+    def _decode_call(self, x, req: DecodeRequest):
+        """One library decode of the clips x (at most max_clips_per_call) as `req` asks, and generate()'s result for it.
+        With a boost: the shared automaton `bl`, the per-clip lists (a BiasBatch that lives for this call) or neither;
+        seeds sample; `scored` asks for token log-probs (greedy) or sequence scores (beams)."""
+        prefix = self._prefix(req)
+        cfg = _lib.WcbGenCfg(req.max_new(self.dims.n_text_ctx), req.min_new_tokens, req.num_beams, req.bias_boost,
+                             int(req.use_graph), int(not req.block))
+        smp = _lib.WcbSampleCfg(req.temperature, req.seeds.ctypes.data_as(C.POINTER(C.c_uint64))) if req.seeds is not None else None
+        bl = self._automaton(req.bias_shared, req.bias_boost)
+        bias_lists, scored = req.bias_lists if req.bias_boost > 0 else None, req.scored
+        self._install_rules(req.rules)
         B, max_new, beams = x.shape[0], cfg.max_new_tokens, cfg.num_beams > 1
         out = torch.empty(B, max_new, dtype=torch.int32, device=self.device)
         lp = torch.zeros(B, max_new, dtype=torch.float32, device=self.device) if scored and not beams else None
@@ -857,7 +643,14 @@ class WhisperCB:
         finally:
             if bb:
                 bb.close()   # the call copied it, as it copied the seeds (also with block=False)
-        return out, steps.value, lp, ss
+        return self._generate_result(out, steps.value, prefix, req.block, req.as_dict, lp, ss, req.timestamps)
+
+    def _prompt_columns(self, prefix, B: int):
+        """(the prompt columns of `sequences`, int64 [B, P]; prompt_lengths [B], None for a shared prefix)."""
+        if isinstance(prefix, _PackedPrompts):
+            return (torch.from_numpy(prefix.rows.astype(np.int64)).to(self.device),
+                    torch.from_numpy(prefix.lengths.astype(np.int64)).to(self.device))
+        return torch.tensor(prefix, dtype=torch.int64, device=self.device)[None].expand(B, -1), None
 
     def _generate_result(self, out, n, prefix, block, as_dict, lp=None, ss=None, timestamps=False):
         """generate()'s return value from a decode's ids [B, max_new] (n columns generated) and its scores, if any."""
@@ -870,14 +663,9 @@ class WhisperCB:
         if not as_dict:
             return self._whisper_trim(ids)
         B = ids.shape[0]
-        if isinstance(prefix, _PackedPrompts):
-            sot = torch.from_numpy(prefix.rows.astype(np.int64)).to(self.device)
-        else:
-            sot = torch.tensor(prefix, dtype=torch.int64, device=self.device)[None].expand(B, -1)
-        res = GenerateOutput(sequences=torch.cat([sot, ids], dim=1), sequences_scores=ss,
+        sot, plen = self._prompt_columns(prefix, B)
+        res = GenerateOutput(sequences=torch.cat([sot, ids], dim=1), sequences_scores=ss, prompt_lengths=plen,
                              segments=self._segments(ids.cpu().numpy()) if timestamps else None)
-        if isinstance(prefix, _PackedPrompts):
-            res.prompt_lengths = torch.from_numpy(prefix.lengths.astype(np.int64)).to(self.device)
         if lp is not None:
             res.token_logprobs = lp[:, :n]
             # Whisper's avg_logprob on the host: each row's tokens up to and including its EOS (a finished row's
@@ -891,80 +679,56 @@ class WhisperCB:
             res.avg_logprob = torch.from_numpy(avg).to(self.device)
         return res
 
-    def _generate_with_fallback(self, x_all, temps, seed, logprob_threshold, compression_ratio_threshold, kw) -> GenerateOutput:
-        """generate(temperature=(t0, t1, ...)): HF's generate_with_fallback rule over generate() calls on the
-        still-failing clips (their mel re-encoded: the rare path pays the encoder again)."""
-        if not temps:
-            raise ValueError("temperature: an empty sequence")
-        B = x_all.shape[0]
-        nb = kw["num_beams"] if kw["num_beams"] is not None else getattr(kw["generation_config"] or self.generation_config,
-                                                                       "num_beams", 1)
-        if int(nb or 1) != 1:
-            raise ValueError("temperature fallback is greedy and sampling only: num_beams must be 1")
-        explicit = None
-        if not isinstance(seed, (int, np.integer)):
-            explicit = [int(v) & _M64 for v in seed]
-            if len(explicit) != B:
-                raise ValueError(f"seed has {len(explicit)} entries, the batch {B} clips")
-        bias_lists, bias_list, bias_spans = kw.pop("bias_lists"), kw.pop("bias_list"), kw.pop("bias_spans")
-        per_utt, boost = kw.pop("per_utterance_bias"), kw["bias_boost"]
-        # the batch's lists once, on the whole batch (as the split path): later attempts decode a subset
-        if bias_lists is None and per_utt and bias_list is None and boost > 0 and bias_spans is not None:
-            bias_lists = self._spans_to_lists(bias_spans)
-        if bias_lists is not None:
-            bias_lists, bias_list = self._clip_lists(bias_lists, bias_list, B), None
-        elif bias_list is None and boost > 0 and bias_spans is not None:
-            bias_list = self._spans_to_phrases(bias_spans)
-        kw.pop("labels")
-        seqs, lps = [None] * B, [None] * B
-        avg, used = np.zeros(B, dtype=np.float32), np.zeros(B, dtype=np.float32)
-        todo = np.arange(B)
-        prompts_all = kw.pop("prompt_ids")
-        ragged = _prompts.is_nested(prompts_all)   # per-clip prompts: a failing clip is re-decoded with its own
-        P = 1 + (len(prompts_all) if prompts_all is not None and not ragged else 0)
-        for i, T in enumerate(temps):
-            if explicit is not None:
-                sd = np.asarray([(explicit[b] + i * 0x9E3779B97F4A7C15) & _M64 for b in todo], dtype=np.uint64)
-            else:
-                sd = clip_seeds(int(seed), 0, B, attempt=i)[todo]
-            idx = torch.as_tensor(todo, device=x_all.device)
-            res = self.generate(x_all[idx] if len(todo) < B else x_all, temperature=T, seed=sd, output_logprobs=True,
-                                bias_list=bias_list, bias_lists=[bias_lists[b] for b in todo] if bias_lists is not None else None,
-                                prompt_ids=[prompts_all[b] for b in todo] if ragged else prompts_all, **kw)
-            if ragged:
-                P = int(res.prompt_lengths.max())   # this attempt's own prompt width
-            ids_h = res.sequences[:, P:].cpu().numpy()
-            lp_h = res.token_logprobs.cpu().numpy()
-            avg_h = res.avg_logprob.cpu().numpy()
-            fail = []
-            for j, b in enumerate(todo):
-                seqs[b], lps[b], avg[b], used[b] = ids_h[j], lp_h[j], avg_h[j], T
-                bad = logprob_threshold is not None and avg_h[j] < logprob_threshold
-                if not bad and compression_ratio_threshold is not None:
-                    bad = compression_ratio(ids_h[j], self.dims.vocab, self.dims.eos_token_id) > compression_ratio_threshold
-                if bad:
-                    fail.append(b)
-            todo = np.asarray(fail, dtype=np.int64)
+    def _join(self, req: DecodeRequest, parts):
+        """One result for the clips of `req` from decodes of some of them (the chunks of a split, the attempts of a
+        fallback). parts: (dst, src, result, P) — rows `src` of `result`, a decode at prompt width P, are clips `dst`
+        of the batch (each a slice or an index tensor). Ids are padded with pad and log-probs with 0 to the widest
+        part that gives a row; the prompt columns are packed again at this batch's width."""
+        results, pad = [r for _, _, r, _ in parts], self.dims.pad_token_id
+
+        def scatter(vals, fill=0.0, dtype=torch.float32):   # [k] or [k, w] of every part -> [B] or [B, widest w]
+            if any(v is None for v in vals):
+                return None
+            flat = vals[0].dim() == 1
+            vals = [v[src].reshape(-1, 1) if flat else v[src] for (_, src, _, _), v in zip(parts, vals)]
+            out = torch.full((req.B, max((v.shape[1] for v in vals if len(v)), default=0)), fill, dtype=dtype, device=self.device)
+            for (dst, _, _, _), v in zip(parts, vals):
+                if len(v):
+                    out[dst, :v.shape[1]] = v
+            return out[:, 0] if flat else out
+
+        if not req.as_dict:   # every part trimmed on its own: Whisper's padding of the joined output
+            return scatter(results, pad, torch.int64)
+        sot, plen = self._prompt_columns(self._prefix(req), req.B)
+        ids = scatter([r.sequences[:, P:] for _, _, r, P in parts], pad, torch.int64)
+        return GenerateOutput(
+            sequences=torch.cat([sot, ids], dim=1), prompt_lengths=plen, token_logprobs=scatter([r.token_logprobs for r in results]),
+            avg_logprob=scatter([r.avg_logprob for r in results]), sequences_scores=scatter([r.sequences_scores for r in results]),
+            # token rules never meet the fallback (resolve() refuses it): the parts are whole chunks, in order
+            segments=[s for r in results for s in r.segments] if req.timestamps else None)
+
+    def _generate_with_fallback(self, x, req: DecodeRequest) -> GenerateOutput:
+        """generate(temperature=(t0, t1, ...)): HF's generate_with_fallback rule. Attempt i decodes the still-failing
+        clips (their mel re-encoded: the rare path pays the encoder again) through _decode, so a failing subset above
+        64 clips splits as any batch does; a clip keeps the first attempt it passes, or the last one."""
+        kept, used, todo = [], np.zeros(req.B, dtype=np.float32), np.arange(req.B)
+        lpt, crt = req.logprob_threshold, req.compression_ratio_threshold
+        for i, T in enumerate(req.temperatures):
+            whole = len(todo) == req.B   # then the caller's tensor itself: no gather
+            sub = req.attempt(i) if whole else req.attempt(i).take(todo)
+            res = self._decode(x if whole else x[torch.as_tensor(todo, device=x.device)], sub)
+            ids_h, avg_h = res.sequences[:, sub.prompt_width:].cpu().numpy(), res.avg_logprob.cpu().numpy()
+            fail = np.asarray([i + 1 < len(req.temperatures) and (   # the last attempt's result stands
+                (lpt is not None and avg_h[j] < lpt) or
+                (crt is not None and compression_ratio(ids_h[j], self.dims.vocab, self.dims.eos_token_id) > crt))
+                for j in range(sub.B)], dtype=bool)
+            used[todo[~fail]] = T
+            kept.append((torch.as_tensor(todo[~fail], device=self.device),
+                         torch.as_tensor(np.flatnonzero(~fail), device=self.device), res, sub.prompt_width))
+            todo = todo[fail]
             if not len(todo):
                 break
-        # joined per clip, padded as the split path pads: ids with pad, log-probs with 0
-        W = max(len(r) for r in seqs)
-        ids = np.full((B, W), self.dims.pad_token_id, dtype=np.int64)
-        lp = np.zeros((B, W), dtype=np.float32)
-        for b in range(B):
-            ids[b, :len(seqs[b])] = seqs[b]
-            lp[b, :len(lps[b])] = lps[b]
-        dev = self.device
-        plen = None
-        if ragged:
-            sot, plen = _prompts.pack_prompts(prompts_all, self.dims.decoder_start_token_id, self.dims.pad_token_id)
-            sot, plen = sot.astype(np.int64), torch.from_numpy(plen.astype(np.int64)).to(dev)
-        else:
-            prefix = ([int(t) for t in prompts_all] if prompts_all is not None else []) + [self.dims.decoder_start_token_id]
-            sot = np.broadcast_to(np.asarray(prefix, dtype=np.int64), (B, len(prefix)))
-        return GenerateOutput(sequences=torch.from_numpy(np.concatenate([sot, ids], axis=1)).to(dev),
-                              token_logprobs=torch.from_numpy(lp).to(dev), avg_logprob=torch.from_numpy(avg).to(dev),
-                              temperatures=torch.from_numpy(used).to(dev), prompt_lengths=plen)
+        return replace(self._join(req, kept), temperatures=torch.from_numpy(used).to(self.device))
 
     def decode_begin(self, encoder_outputs, prompt_ids=None, bias_list=None, bias_boost: float = 0.0,
                      min_new_tokens: int = 0, num_beams: int = 1, max_length: Optional[int] = None,
@@ -986,29 +750,19 @@ class WhisperCB:
         then the winners' perturbed values. `return_timestamps` / `suppress_tokens` / `begin_suppress_tokens` /
         `max_initial_timestamp`: generate()'s token rules for every step of this decode (greedy only; timestamps
         not with sampling: ValueError)."""
-        rules = self._rules_key_of(return_timestamps, suppress_tokens, begin_suppress_tokens, max_initial_timestamp)
-        if rules is not None:
-            if int(num_beams) != 1:
-                raise ValueError("suppress_tokens / begin_suppress_tokens / return_timestamps are greedy only: num_beams must be 1")
-            if return_timestamps and float(temperature) > 0.0:
-                raise ValueError("return_timestamps with sampling is not supported")
+        T, nb = _request.sampling_temperature(temperature), int(num_beams)
+        rules = _request.rules_key(self.dims, return_timestamps, suppress_tokens, begin_suppress_tokens, max_initial_timestamp)
+        if rules is not None and nb != 1:
+            raise ValueError("suppress_tokens / begin_suppress_tokens / return_timestamps are greedy only: num_beams must be 1")
+        if return_timestamps and T > 0.0:
+            raise ValueError("return_timestamps with sampling is not supported")
+        if T > 0.0 and nb != 1:
+            raise ValueError("sampling (temperature > 0) is greedy only: num_beams must be 1")
         enc = self._encoder_state(encoder_outputs)   # [B, 1500, d] checked: the library copies B·1500·d
         B = enc.shape[0]
         if B > 64:
             raise ValueError("decode_begin takes at most 64 clips")
-        T = float(temperature)
-        if not (T >= 0.0 and math.isfinite(T)):
-            raise ValueError(f"temperature must be finite and >= 0, got {temperature!r}")
-        seeds = None
-        if T > 0.0:
-            if int(num_beams) != 1:
-                raise ValueError("sampling (temperature > 0) is greedy only: num_beams must be 1")
-            if isinstance(seed, (int, np.integer)):
-                seeds = clip_seeds(int(seed), 0, B)
-            else:
-                seeds = np.ascontiguousarray(np.asarray([int(v) & _M64 for v in seed], dtype=np.uint64))
-                if seeds.shape[0] != B:
-                    raise ValueError(f"seed has {seeds.shape[0]} entries, the batch {B} clips")
+        seeds = _request.seed_array(seed, B) if T > 0.0 else None
         start = self.dims.decoder_start_token_id
         packed = None
         if _prompts.is_nested(prompt_ids) and not isinstance(prompt_ids, np.ndarray):
@@ -1016,7 +770,7 @@ class WhisperCB:
             if len(plists) != B:
                 raise ValueError(f"prompt_ids holds {len(plists)} prompts, the batch {B} clips")
             if len({len(p) for p in plists}) > 1:   # ragged: the left-padded form (equal lengths: the [B, P] path)
-                if int(num_beams) != 1:
+                if nb != 1:
                     raise ValueError("per-clip prompts of different lengths are greedy only: num_beams must be 1")
                 packed = _PackedPrompts(*_prompts.pack_prompts(plists, start, self.dims.pad_token_id))
             prompt_ids = plists
@@ -1029,30 +783,19 @@ class WhisperCB:
             elif p.ndim != 2 or p.shape[0] != B:
                 raise ValueError(f"prompt_ids must be one prompt or a [{B}, P] array, got shape {p.shape}")
             pre = np.ascontiguousarray(np.concatenate([p, np.full((B, 1), start, np.int32)], axis=1))
-        if bias_lists is not None:
-            bias_lists, bias_list = self._clip_lists(bias_lists, bias_list, B), None
-        if isinstance(bias_list, BiasList):   # a prebuilt automaton, as generate() accepts
-            bl = bias_list if bias_boost > 0 else None
-        else:
-            bl = self.bias_list(bias_list) if (bias_list and bias_boost > 0) else None
+        shared, bias_lists = _request.bias_source(B, bias_list, bias_lists, bias_boost)
+        bl = self._automaton(shared, bias_boost)
         st = C.c_void_p()
-        nb = int(num_beams)
         self._install_rules(rules)
+        flat = (pre.ctypes.data, pre.shape[1]) if pre is not None else (None, 1)
         if packed is not None:
-            _lib.check(self._lib.wcb_decode_begin_prompted(self._h, _ptr(enc), B, packed.rows.ctypes.data, packed.rows.shape[1],
-                                                           packed.lengths.ctypes.data, float(bias_boost), int(min_new_tokens),
-                                                           C.byref(st), _stream(self.device)), self._h,
-                       "wcb_decode_begin_prompted")
+            name, args = "wcb_decode_begin_prompted", (packed.rows.ctypes.data, packed.rows.shape[1], packed.lengths.ctypes.data)
         elif nb > 1 and max_length is not None:
-            _lib.check(self._lib.wcb_decode_begin_beams(self._h, _ptr(enc), B, nb, pre.ctypes.data if pre is not None else None,
-                                                        pre.shape[1] if pre is not None else 1, int(max_length),
-                                                        float(bias_boost), int(min_new_tokens), C.byref(st),
-                                                        _stream(self.device)), self._h, "wcb_decode_begin_beams")
+            name, args = "wcb_decode_begin_beams", (nb,) + flat + (int(max_length),)
         else:
-            _lib.check(self._lib.wcb_decode_begin(self._h, _ptr(enc), B, nb, pre.ctypes.data if pre is not None else None,
-                                                  pre.shape[1] if pre is not None else 1, float(bias_boost),
-                                                  int(min_new_tokens), C.byref(st), _stream(self.device)), self._h,
-                       "wcb_decode_begin")
+            name, args = "wcb_decode_begin", (nb,) + flat
+        _lib.check(getattr(self._lib, name)(self._h, _ptr(enc), B, *args, float(bias_boost), int(min_new_tokens), C.byref(st),
+                                            _stream(self.device)), self._h, name)
         dec = StepDecoder(self, st, B, bl, nb)
         if logprobs:   # greedy only (wcb.h): every step records the log-prob of its token
             _lib.check(self._lib.wcb_decode_enable_logprobs(self._h, st), self._h, "wcb_decode_enable_logprobs")
@@ -1096,32 +839,7 @@ class WhisperCB:
     # ------------------------------------------------------------------------- token timestamps
     def _align_args(self, B: int, alignment_heads, num_frames, median_filter_width) -> dict:
         """The checked alignment arguments (ValueError for what wcb_align refuses)."""
-        W = int(median_filter_width)
-        if W < 1 or W % 2 == 0:
-            raise ValueError(f"median_filter_width must be odd and positive, got {median_filter_width!r}")
-        if W > 15:
-            raise ValueError("median_filter_width above 15 is not supported")
-        heads = None
-        if alignment_heads is not None:
-            heads = [(int(l), int(h)) for l, h in alignment_heads]
-            if not heads:
-                raise ValueError("alignment_heads is empty")
-            for l, h in heads:
-                if not (0 <= l < self.dims.n_layers and 0 <= h < self.dims.n_heads):
-                    raise ValueError(f"alignment head ({l}, {h}) outside {self.dims.n_layers} layers x {self.dims.n_heads} heads")
-            for l in {l for l, _ in heads}:
-                if sum(1 for x, _ in heads if x == l) > 32:
-                    raise ValueError("more than 32 alignment heads in one layer")
-        nf = None
-        if num_frames is not None:
-            nf = np.asarray(num_frames, dtype=np.int64).reshape(-1)
-            if nf.shape[0] == 1 and B > 1:
-                nf = np.repeat(nf, B)
-            if nf.shape[0] != B:
-                raise ValueError(f"num_frames has {nf.shape[0]} entries, the batch {B} clips")
-            if (nf < 2 * W).any() or (nf > 2 * self.dims.n_audio_ctx).any():
-                raise ValueError(f"num_frames must lie in [{2 * W}, {2 * self.dims.n_audio_ctx}]")
-        return dict(heads=heads, num_frames=nf, width=W)
+        return _request.align_args(self.dims, B, alignment_heads, num_frames, median_filter_width)
 
     def _align_call(self, enc, ids: torch.Tensor, prefix, akw, nf, matrix: bool = False):
         """wcb_align on one batch of at most 64 clips: ids int32 [B, n] (device) -> frames int32 [B, n] (and the cost
@@ -1138,7 +856,7 @@ class WhisperCB:
         del keep
         return (frames, mat) if matrix else frames
 
-    def _attach_token_timestamps(self, res: GenerateOutput, input_features, P: int, akw) -> GenerateOutput:
+    def _attach_token_timestamps(self, res: GenerateOutput, x: torch.Tensor, P: int, akw) -> GenerateOutput:
         """token_timestamps (and words) of a finished generate(): through the encoder state the decode left in its
         context when the library still holds it for exactly this batch (one library call decoded it: the library's own
         check, WCB_ERR_STATE otherwise), else re-encoded in batches of at most 64 clips."""
@@ -1156,7 +874,6 @@ class WhisperCB:
             except _lib.WcbStateError:
                 frames = None
         if frames is None:
-            x = self._features(input_features)
             parts = []
             for i in range(0, B, 64):
                 enc = self.encode(x[i:i + 64])
