@@ -447,6 +447,43 @@ int wcb_op_dtw(const float* M, int N, int m_max, int S_ld, const int32_t* lens, 
 int wcb_dtw_host(const float* M, int m, int S, long ld, int32_t* frames, int n_out, int32_t* path_text,
                  int32_t* path_time, int32_t* path_len);
 
+/* ---- long-form transcription: audio past 30 s (HF WhisperGenerationMixin's long-form branch; the seek loop itself runs
+ * on the host, whisper_context_biasing_amd/longform.py; semantics: DESIGN.md §5g).
+ * wcb_log_mel_long: the feature extractor with truncation = False, padding = "longest": pcm f32 DEVICE [B][pcm_stride],
+ * clip b's first n_valid[b] samples valid (HOST [B]) and the rest up to n_total read as zero, reflect padding resolved at
+ * n_total -> mel_out f32 DEVICE [B][n_mel][T_ld], T = n_total / 160 frames written per row (columns T .. T_ld - 1 are not
+ * touched), the max - 8 clamp over all T frames of the clip. Like wcb_log_mel it needs no weights (any created handle).
+ * WCB_ERR_ARG: B outside 1..64, n_total < 800 or > pcm_stride, T_ld < T, n_valid[b] outside [0, n_total]. */
+int wcb_log_mel_long(wcb_handle* h, const float* pcm, int B, const int32_t* n_valid, int n_total, int64_t pcm_stride,
+                     float* mel_out, int T_ld, void* stream);
+/* The windows of one decode: row r is the 3000-frame window of clip clip_idx[r] that starts at mel frame seek[r] and
+ * holds seek_num_frames[r] frames, zero (0.0 in the feature domain, HF _get_input_segment) from there to frame 3000.
+ * mel f32 DEVICE [clips][n_mel][T_ld] with T valid frames per row; the three int arrays are HOST [rows] and are copied
+ * on the encoder stream (free on return). The cut writes the encoder's conv-input layout directly: no [rows][n_mel][3000]
+ * intermediate. WCB_ERR_ARG: rows outside 1..64, clip_idx outside [0, clips), seek < 0, seek_num_frames outside
+ * [1, 3000], seek + seek_num_frames > T, T > T_ld. */
+typedef struct { const float* mel; int clips, T, T_ld;
+                 const int32_t* clip_idx; const int32_t* seek; const int32_t* seek_num_frames; } wcb_windows;
+/* wcb_encode after the cut: enc_out [rows][1500][d] as wcb_encode's. With T = T_ld = 3000, seek 0 and 3000 frames it is
+ * bit for bit wcb_encode of the same features. */
+int wcb_encode_windows(wcb_handle* h, const wcb_windows* w, int rows, void* enc_out, void* stream);
+/* wcb_generate_prompted's greedy, unsampled form on the windows (out_logprobs may be NULL), plus out_no_speech f32 DEVICE
+ * [rows] (nullable; needs out_logprobs, else WCB_ERR_UNSUPPORTED): no_speech_prob[r] = exp(logit[<|nospeech|>] -
+ * logsumexp(raw logits)) at the start token's position — the logits of generation step 0 — with <|nospeech|> the id
+ * before <|notimestamps|>. The scored finalize writes it from the logsumexp it merges for the token log-probs: no logits
+ * leave the chip; boost, deny lists and grammar never enter it. Decodes with it on replay graphs of their own; with it
+ * off every path launches what it launched before. num_beams > 1: WCB_ERR_UNSUPPORTED. */
+int wcb_generate_windows(wcb_handle* h, const wcb_windows* w, int rows, const wcb_gen_cfg* cfg, const wcb_bias* bias,
+                         const wcb_bias_batch* bb, const int32_t* prompts, int prompt_ld, const int32_t* prompt_len,
+                         int32_t* out_ids, float* out_logprobs, float* out_no_speech, int32_t* out_steps, void* stream);
+/* step-wise: after wcb_decode_enable_logprobs and before the first step (else WCB_ERR_STATE; beam state:
+ * WCB_ERR_UNSUPPORTED); wcb_decode_no_speech copies the [B] probabilities out once a step was taken. */
+int wcb_decode_enable_no_speech(wcb_handle* h, wcb_state* st);
+int wcb_decode_no_speech(wcb_handle* h, wcb_state* st, float* out, void* stream);
+/* the window cut on caller operands: xt [rows][3002][n_mel] in `dtype`; arguments and errors as wcb_windows. Blocks. */
+int wcb_op_window_cut(int dtype, const float* mel, int clips, int n_mel, int T, int T_ld, int rows, const int32_t* clip_idx,
+                      const int32_t* seek, const int32_t* seek_num_frames, void* xt, void* stream);
+
 /* debug counters by name (not part of wcb_profile_read): "graph_captures" = decode graphs instantiated so
  * far on this handle. Unknown name: WCB_ERR_ARG. */
 int wcb_debug_counter(const wcb_handle* h, const char* name, int64_t* out);

@@ -68,6 +68,20 @@ def align_cfg(heads=None, median_width=7, num_frames=None):
     return cfg, (hd, nf)
 
 
+class WcbWindows(C.Structure):
+    _fields_ = [("mel", C.c_void_p), ("clips", C.c_int), ("T", C.c_int), ("T_ld", C.c_int),
+                ("clip_idx", C.POINTER(C.c_int32)), ("seek", C.POINTER(C.c_int32)), ("seek_num_frames", C.POINTER(C.c_int32))]
+
+
+def windows(mel_ptr, clips, T, T_ld, clip_idx, seek, seek_num_frames):
+    """A WcbWindows and the int arrays it points into (keep both alive for the call)."""
+    import numpy as np
+    p32 = C.POINTER(C.c_int32)
+    arrs = tuple(np.ascontiguousarray(np.asarray(a, dtype=np.int32)) for a in (clip_idx, seek, seek_num_frames))
+    w = WcbWindows(mel_ptr, int(clips), int(T), int(T_ld), *(a.ctypes.data_as(p32) for a in arrs))
+    return w, arrs
+
+
 class WcbTensorView(C.Structure):
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("dtype", C.c_int), ("ndim", C.c_int),
                 ("shape", C.c_int64 * 4), ("stride", C.c_int64 * 4)]
@@ -122,6 +136,13 @@ SIGNATURES = {
     "wcb_decode_begin_prompted": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, C.c_float, C.c_int, C.POINTER(_P), _P]),
     "wcb_op_attention_decode_window": (C.c_int, [C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P,
                                                  C.c_int, _P]),
+    "wcb_log_mel_long": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int64, _P, C.c_int, _P]),
+    "wcb_encode_windows": (C.c_int, [_P, C.POINTER(WcbWindows), C.c_int, _P, _P]),
+    "wcb_generate_windows": (C.c_int, [_P, C.POINTER(WcbWindows), C.c_int, C.POINTER(WcbGenCfg), _P, _P, _P, C.c_int, _P,
+                                       _P, _P, _P, C.POINTER(C.c_int32), _P]),
+    "wcb_decode_enable_no_speech": (C.c_int, [_P, _P]),
+    "wcb_decode_no_speech": (C.c_int, [_P, _P, _P, _P]),
+    "wcb_op_window_cut": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "wcb_sample_noise": (C.c_int, [C.c_uint64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]),
     "wcb_set_token_rules": (C.c_int, [_P, C.POINTER(WcbTokenRules)]),
     "wcb_token_rules_apply_host": (C.c_int, [C.POINTER(WcbTokenRules), C.c_int, C.c_int, _P, C.c_int, _P]),

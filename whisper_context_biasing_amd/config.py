@@ -103,6 +103,17 @@ def timestamp_ids(dims):
     return timestamp_begin, timestamp_begin - 1
 
 
+def no_speech_token_id(dims) -> int:
+    """<|nospeech|> (<|nocaptions|> in the older vocabularies): the id right before <|notimestamps|>, as HF's
+    WhisperNoSpeechDetection takes it (51864: 50361, 51865: 50362, 51866: 50363)."""
+    return timestamp_ids(dims)[1] - 1
+
+
+def start_of_prev_token_id(dims) -> int:
+    """<|startofprev|>: two ids before <|notimestamps|> (51864: 50360, 51865: 50361, 51866: 50362)."""
+    return timestamp_ids(dims)[1] - 2
+
+
 def parse_segments(ids, timestamp_begin, eos=None):
     """Segments of one row of generated ids decoded with timestamps: a list of (start_s, end_s, token_ids). The
     text between one timestamp token and the next is a segment, time = (token - timestamp_begin) * 0.02 s; of a

@@ -277,6 +277,9 @@ __global__ __launch_bounds__(64) void select_finalize_kernel(SelectArgs a) {
     if (a.out_score) a.out_score[m] = fin ? 0.f : bv;
     if (a.out_logprob)   // the chosen token's raw logit against the row's logsumexp
       a.out_logprob[(long)m * a.out_ld + step] = fin ? 0.f : a.logits[(long)m * a.ld + tok] - (lm + logf(ls));
+    // no-speech probability (with out_logprob): step 0 scores the start token's position, so its raw softmax at
+    // <|nospeech|> is Whisper's no_speech_prob — one float per row from the logsumexp just merged
+    if (a.out_nsp && step == 0) a.out_nsp[m] = expf(a.logits[(long)m * a.ld + a.nsp_token] - (lm + logf(ls)));
     const bool nf = fin || tok == a.eos;
     a.finished[m] = nf ? 1 : 0;
     // one 64-bit counter: arrivals in the low word, unfinished rows in the high word, so the row that

@@ -249,6 +249,14 @@ void logmel_power_mel(const float* pcm, long pcm_stride, int n_samples, int B, c
 void logmel_normalize(float* mel, const unsigned* clip_max, int B, int n_mel, hipStream_t s);
 void mel_to_conv_input(DType t, const float* mel, int B, int n_mel, void* xt, long clip_stride,
                        hipStream_t s);
+// long-form (k_logmel.hip): the log-mel of whole recordings (n_valid DEVICE [B], T = n_total / 160 frames into rows of
+// T_ld floats, power/mel and normalise passes) and the window cut straight into the conv-input layout (clip_idx, seek,
+// nfr DEVICE [rows]; mel f32 [clips][n_mel][T_ld])
+void logmel_long(const float* pcm, long pcm_stride, const int* n_valid, int n_total, int B, const float* dft, const void* dft3,
+                 const int* mel_lo, const int* mel_hi, const float* mel_w, int n_mel, float* mel_out, int T_ld,
+                 unsigned* clip_max, hipStream_t s);
+void mel_window_to_conv_input(DType t, const float* mel, int n_mel, int T_ld, const int* clip_idx, const int* seek, const int* nfr,
+                              int rows, void* xt, long row_stride, hipStream_t s);
 
 // Per-utterance bias lists: a forest of Aho-Corasick automata in ONE state space (trans_* / st_* of the
 // selection arguments stay global CSR arrays), a root state per clip, and each clip's gated root children
@@ -307,6 +315,9 @@ struct SelectArgs {
   // instantiations only: ts.on with seeds is refused by the runtime
   const uint32_t* deny = nullptr; const uint32_t* deny0 = nullptr;
   TsRule ts; int* ts_state = nullptr;
+  // no-speech probability (out_nsp non-null; needs out_logprob, whose merged logsumexp it reuses): at
+  // step 0 out_nsp[m] = exp(logits[m][nsp_token] − lse) over the raw logits; later steps leave it alone
+  float* out_nsp = nullptr; int nsp_token = 0;
 };
 void select_greedy(const SelectArgs& a, hipStream_t s);          // vocabulary pass + finalize
 void select_finalize(const SelectArgs& a, hipStream_t s);        // partials already written (fused LM head)

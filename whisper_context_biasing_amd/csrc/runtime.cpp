@@ -153,6 +153,7 @@ struct wcb_state {
   bool logprobs = false; // wcb_decode_enable_logprobs: every step also writes its column of the context's lpbuf
   bool sampling = false; // wcb_decode_enable_sampling: every step draws its tokens (the context's samp words)
   bool ragged = false;   // per-clip prompts of different lengths (left-padded to P): every step reads the context's poff
+  bool no_speech = false; // wcb_decode_enable_no_speech: the first step also writes the context's nsp floats
 };
 
 // lean decode projection classes stamped inside the replayed decode graph (stamps pass), by region
@@ -205,8 +206,10 @@ struct DecCtx {
   // the captured decode steps, one slot per kind of call: a ruled (wcb_set_token_rules), a sampled and a scored
   // (token log-probs) decode each launch other kernels or arguments, so every combination replays its own graphs
   // and no kind of call evicts another's
-  StepGraphs graphs[8];
-  StepGraphs& graphs_of(bool ruled, bool sampled, bool scored) { return graphs[4 * ruled + 2 * sampled + scored]; }
+  StepGraphs graphs[16];
+  StepGraphs& graphs_of(bool ruled, bool sampled, bool scored, bool no_speech = false) {
+    return graphs[8 * no_speech + 4 * ruled + 2 * sampled + scored];
+  }
   void drop_graphs() {
     for (StepGraphs& g : graphs) g.drop();
   }
@@ -224,6 +227,9 @@ struct DecCtx {
   // graph key only the fact); the left-padded prompts and the offsets go up on the decode stream from the pinned
   // p_stage, as the forest does
   DevBuf poff;
+  // no-speech probability (wcb_generate_windows, wcb_decode_enable_no_speech): one float per row [64], written by
+  // the scored finalize at step 0; allocated once and never moved (the graphs of such decodes hold its address)
+  DevBuf nsp;
   int* p_stage = nullptr;
   size_t p_stage_words = 0;
   hipEvent_t ev_pcopy = nullptr;
@@ -406,6 +412,7 @@ struct wcb_handle {
   void* tok_emb_fm = nullptr;   // 16-bit: fragment-major copy of tok_emb for the greedy LM head
   // mel tables
   DevBuf dft, dft3, mel_lo, mel_hi, mel_w, clip_max;
+  DevBuf win_ints;   // long-form: clip index, seek and frame count of every window row [3][kWinRows], or n_valid [B] (stream he)
   // encoder workspace
   int enc_B = 0;
   DevBuf xt, hbuf, x, h, qkv, att, ffn, encout;
@@ -721,6 +728,7 @@ void wcb_destroy(wcb_handle* h) {
     if (D.done_h) (void)hipHostFree(D.done_h);
     D.forest.release();
     D.poff.release();
+    D.nsp.release();
     if (D.p_stage) (void)hipHostFree(D.p_stage);
     if (D.ev_pcopy) (void)hipEventDestroy(D.ev_pcopy);
     if (D.f_stage) (void)hipHostFree(D.f_stage);
@@ -732,7 +740,7 @@ void wcb_destroy(wcb_handle* h) {
     if (D.hs) (void)hipStreamDestroy(D.hs);
   }
   for (auto& b : h->owned) b.release();
-  for (DevBuf* b : {&h->dft, &h->dft3, &h->mel_lo, &h->mel_hi, &h->mel_w, &h->clip_max, &h->xt, &h->hbuf, &h->x, &h->h,
+  for (DevBuf* b : {&h->dft, &h->dft3, &h->mel_lo, &h->mel_hi, &h->mel_w, &h->clip_max, &h->win_ints, &h->xt, &h->hbuf, &h->x, &h->h,
                     &h->qkv, &h->att, &h->ffn, &h->encout, &h->stamps, &h->stamp_acc, &h->dev_err, &h->rules_deny,
                     &h->rules_deny0, &h->al_w, &h->al_M, &h->al_tf, &h->al_lens, &h->al_frames, &h->al_prefix, &h->al_trace})
     b->release();
@@ -1197,13 +1205,46 @@ void run_gemm(wcb_handle* h, const char* cls, const GemmArgs& g0) {
 
 // WhisperEncoder.forward ([tf] modeling_whisper.py:592-646) on mel f32 [B][n_mel][3000]; the final
 // LayerNorm writes [B][1500][d] to enc_out (h->encout when null)
-void encode_impl(wcb_handle* h, const float* mel, int B, void* enc_out) {
+// the windows of a long-form call: rows of 3000 frames cut from long features (wcb_windows, checked by check_windows)
+constexpr int kWinRows = 64;
+constexpr int kTimestampTokens = 1501;   // <|0.00|> .. <|30.00|>, the last ids of every Whisper vocabulary
+void check_windows(const wcb_windows* w, int rows) {
+  REQUIRE(w && w->mel && w->clip_idx && w->seek && w->seek_num_frames, "windows: mel, clip_idx, seek and seek_num_frames are required");
+  REQUIRE(rows >= 1 && rows <= kWinRows, "windows: 1 .. 64 rows per call");
+  REQUIRE(w->clips >= 1 && w->T >= 1 && w->T_ld >= w->T, "windows: clips >= 1 and 1 <= T <= T_ld are required");
+  for (int r = 0; r < rows; ++r) {
+    const std::string at = "windows row " + std::to_string(r) + ": ";
+    REQUIRE(w->clip_idx[r] >= 0 && w->clip_idx[r] < w->clips, at + "clip index outside [0, clips)");
+    REQUIRE(w->seek[r] >= 0, at + "seek < 0");
+    REQUIRE(w->seek_num_frames[r] >= 1 && w->seek_num_frames[r] <= kFrames, at + "seek_num_frames outside [1, 3000]");
+    REQUIRE((long)w->seek[r] + w->seek_num_frames[r] <= w->T, at + "seek + seek_num_frames > T");
+  }
+}
+// the three int arrays onto the encoder stream (by value in a launch: the caller's arrays are free on return)
+const int* upload_windows(wcb_handle* h, const wcb_windows* w, int rows) {
+  h->win_ints.ensure((size_t)3 * kWinRows * 4);   // once: 3 x 64 ints
+  int v[3 * kWinRows] = {};
+  for (int r = 0; r < rows; ++r) {
+    v[r] = w->clip_idx[r]; v[kWinRows + r] = w->seek[r]; v[2 * kWinRows + r] = w->seek_num_frames[r];
+  }
+  write_i32(h->win_ints.as<int>(), v, 3 * kWinRows, h->he);
+  return h->win_ints.as<int>();
+}
+
+void encode_impl(wcb_handle* h, const float* mel, int B, void* enc_out, const wcb_windows* win = nullptr) {
   ensure_enc_ws(h, B);
   const int d = h->d.d_model, S = h->S(), nm = h->d.n_mel, H = h->H();
   const long M = (long)B * S;
   const size_t e = esize(h->d.dtype);
   const long xt_stride = (long)(kFrames + 2) * nm, hb_stride = (long)(kFrames + 1) * d;
-  h->timed("mel_to_conv_input", 0, 0, h->he, [&] { mel_to_conv_input(h->dt, mel, B, nm, h->xt.p, xt_stride, h->he); });
+  if (win) {   // long-form: row b is a window of the long features, cut on the chip
+    const int* wi = upload_windows(h, win, B);
+    h->timed("mel_window_cut", 0, 0, h->he, [&] {
+      mel_window_to_conv_input(h->dt, win->mel, nm, win->T_ld, wi, wi + kWinRows, wi + 2 * kWinRows, B, h->xt.p, xt_stride, h->he);
+    });
+  } else {
+    h->timed("mel_to_conv_input", 0, 0, h->he, [&] { mel_to_conv_input(h->dt, mel, B, nm, h->xt.p, xt_stride, h->he); });
+  }
   {  // conv1 + GELU → hbuf rows 1..3000 of every clip (row 0 = conv2's zero padding)
     GemmArgs g = rowgemm(h->xt.p, nm, h->conv1_w, B * kFrames, d, h->k1pad, (char*)h->hbuf.p + d * e, d);
     g.a_Mb = kFrames; g.a_strideB = xt_stride;
@@ -1431,6 +1472,9 @@ struct StepCfg {
   // greedy, ragged prompts: the slot offset of every row (the context's poff) — the self-attention windows and the
   // position embeddings shift by it. Null: the step as it always was
   const int* pos_off = nullptr;
+  // greedy select with token log-probs: the first step also writes every row's no-speech probability here (the
+  // context's nsp). Null: the step as it always was
+  float* nsp_out = nullptr;
 };
 
 // the capture of one teacher-forced pass of wcb_align: per layer the selected (head, slot in the list) pairs; the
@@ -1862,6 +1906,7 @@ void decode_step(wcb_handle* h, const StepCfg& c) {
     }
     if (c.samp) { s.inv_t = reinterpret_cast<const float*>(c.samp); s.seeds = c.samp + 1; }
     s.deny = c.deny; s.deny0 = c.deny0; s.ts = c.ts; s.ts_state = ri.ts_state;
+    if (c.nsp_out && c.logprob_out) { s.out_nsp = c.nsp_out; s.nsp_token = h->d.vocab - kTimestampTokens - 2; }
     if (c.embedded) {   // the next step's input embedding in the same launch (embed()'s outputs)
       const bool r32 = h->dec_gemm && lnf_possible(h);
       s.emb = h->tok_emb; s.pemb = h->dec_pos; s.n_pos = h->d.n_text_ctx; s.d = d; s.dtype = h->dt;
@@ -2185,6 +2230,9 @@ struct GenCall {
   const wcb_sample_cfg* smp = nullptr;
   // per-clip prompts (wcb_generate_prompted): HOST [B][prompt_ld] left-padded, lengths HOST [B]; prefix is then null
   const int32_t* prompts = nullptr; int prompt_ld = 0; const int32_t* prompt_len = nullptr;
+  // long-form (wcb_generate_windows): the B rows are windows of long features (mel is then null), and the no-speech
+  // probability of every row [B] (nullable; needs out_logprobs)
+  const wcb_windows* win = nullptr; float* out_no_speech = nullptr;
 };
 
 // the step-wise decode context, after the check every step-wise entry point makes of its state (`what`: the
@@ -2225,6 +2273,38 @@ int wcb_encode(wcb_handle* h, const float* mel, int B, void* enc_out, void* stre
   });
 }
 
+int wcb_log_mel_long(wcb_handle* h, const float* pcm, int B, const int32_t* n_valid, int n_total, int64_t pcm_stride,
+                     float* mel_out, int T_ld, void* stream) {
+  return guarded(h, [&] {
+    REQUIRE(h && pcm && mel_out && n_valid && B > 0 && B <= kWinRows, "bad argument (1 .. 64 clips)");
+    REQUIRE(n_total >= 800 && pcm_stride >= n_total, "n_total must be at least 800 samples and at most pcm_stride");
+    REQUIRE(T_ld >= n_total / 160, "T_ld < n_total / 160 frames");
+    for (int b = 0; b < B; ++b) REQUIRE(n_valid[b] >= 0 && n_valid[b] <= n_total, "n_valid outside [0, n_total]");
+    if ((size_t)B * 4 > h->clip_max.bytes) { quiesce(h); h->clip_max.ensure((size_t)std::max(B, h->enc_B) * 4); }
+    h->win_ints.ensure((size_t)3 * kWinRows * 4);
+    sync_in(h, stream, h->he);
+    write_i32(h->win_ints.as<int>(), n_valid, B, h->he);
+    h->timed("log_mel_long", 0, (double)B * (n_total * 4.0 + h->d.n_mel * (n_total / 160) * 4.0 * 3), h->he, [&] {
+      logmel_long(pcm, (long)pcm_stride, h->win_ints.as<int>(), n_total, B, h->dft.as<float>(), h->mel_split ? h->dft3.p : nullptr,
+                  h->mel_lo.as<int>(), h->mel_hi.as<int>(), h->mel_w.as<float>(), h->d.n_mel, mel_out, T_ld,
+                  h->clip_max.as<unsigned>(), h->he);
+    });
+    sync_out(h, stream, h->he);
+  });
+}
+
+int wcb_encode_windows(wcb_handle* h, const wcb_windows* w, int rows, void* enc_out, void* stream) {
+  return guarded(h, [&] {
+    REQUIRE(h, "bad argument");
+    check_windows(w, rows);
+    if (!h->ready) throw WcbError(WCB_ERR_STATE, "weights not finalized");
+    ensure_enc_ws(h, rows);
+    sync_in(h, stream, h->he);
+    encode_impl(h, nullptr, rows, enc_out, w);
+    sync_out(h, stream, h->he);
+  });
+}
+
 // every wcb_generate* entry point: encode, then decode greedily or by beam search
 static void generate_impl(wcb_handle* h, const GenCall& c) {
   {
@@ -2253,7 +2333,10 @@ static void generate_impl(wcb_handle* h, const GenCall& c) {
     REQUIRE(R <= 64 * DecCtx::kMaxSub, "batch x num_beams > 512 rows per call: split the batch");
     REQUIRE(cfg->bias_boost >= 0.f, "bias_boost must be >= 0");
     REQUIRE(cfg->max_new_tokens >= 1, "max_new_tokens must be >= 1");
-    REQUIRE(c.mel != nullptr, "mel is required");
+    REQUIRE(c.mel != nullptr || c.win != nullptr, "mel is required");
+    if (c.win) check_windows(c.win, B);
+    if (c.out_no_speech && !c.out_logprobs)
+      throw WcbError(WCB_ERR_UNSUPPORTED, "the no-speech probability reuses the token log-probs' logsumexp: out_logprobs is required");
     const bool prompted = c.prompts || c.prompt_len;
     if (prompted) check_prompts(c.prompts, c.prompt_ld, c.prompt_len, B, nb);
     const int P = prompted ? c.prompt_ld : c.prefix ? c.prefix_len : 1;
@@ -2289,10 +2372,10 @@ static void generate_impl(wcb_handle* h, const GenCall& c) {
     sync_in(h, c.stream, h->he);
     HIPCHK(hipStreamWaitEvent(h->he, h->ev_dec[buf], 0));
     if (xm == 1) {   // the decode reads the encoder output itself (re-laid out for the stream when xenc_fm)
-      encode_impl(h, c.mel, B, xenc_fm_on(h) ? nullptr : h->xkv2[buf].p);
+      encode_impl(h, c.mel, B, xenc_fm_on(h) ? nullptr : h->xkv2[buf].p, c.win);
       if (xenc_fm_on(h)) fill_xenc(h, buf, h->encout.p, B, h->he);
     } else {
-      encode_impl(h, c.mel, B, nullptr);
+      encode_impl(h, c.mel, B, nullptr, c.win);
       h->timed_wall("xkv_gemm_total", h->he, [&] { cross_kv(h, B, buf, h->encout.p); });
     }
     HIPCHK(hipEventRecord(h->ev_xkv[buf], h->he));
@@ -2315,6 +2398,10 @@ static void generate_impl(wcb_handle* h, const GenCall& c) {
       HIPCHK(hipMemsetAsync(D.lpbuf.p, 0, (size_t)R * out_ld * 4, D.hs));
     }
     if (smp) sc.samp = install_sampling(D, smp->temperature, smp->seeds, R);
+    if (c.out_no_speech) {
+      D.nsp.ensure((size_t)kWinRows * 4);
+      sc.nsp_out = D.nsp.as<float>();
+    }
     const bool ruled = nb == 1 && h->rules_on;
     if (ruled) apply_rules(h, sc);
     decode_prompt(h, sc, P, c.prefix != nullptr || prompted);
@@ -2340,7 +2427,7 @@ static void generate_impl(wcb_handle* h, const GenCall& c) {
     // string (never the seeds or the temperature), so no kind of call evicts another's.
     const int chunk = h->steps_per_graph;
     int done = 0, steps = 0;
-    StepGraphs& g = D.graphs_of(ruled, smp != nullptr, c.out_logprobs != nullptr);
+    StepGraphs& g = D.graphs_of(ruled, smp != nullptr, c.out_logprobs != nullptr, c.out_no_speech != nullptr);
     if (use_graph && (!g.one || g.key != key)) capture_steps(h, sc, g, key);
     // Natural-EOS mode (reference decoding) polls the device "all finished" step one chunk behind:
     // chunk k+1 is queued before the host waits for chunk k's flag, so the GPU never idles on the
@@ -2411,6 +2498,8 @@ static void generate_impl(wcb_handle* h, const GenCall& c) {
     HIPCHK(hipMemcpyAsync(c.out_ids, D.outbuf.p, (size_t)B * out_ld * 4, hipMemcpyDeviceToDevice, D.hs));
     if (c.out_logprobs)
       HIPCHK(hipMemcpyAsync(c.out_logprobs, D.lpbuf.p, (size_t)B * out_ld * 4, hipMemcpyDeviceToDevice, D.hs));
+    if (c.out_no_speech)
+      HIPCHK(hipMemcpyAsync(c.out_no_speech, D.nsp.p, (size_t)B * 4, hipMemcpyDeviceToDevice, D.hs));
     HIPCHK(hipEventRecord(h->ev_dec[buf], D.hs));
     *c.out_steps = std::min(done, max_new);
     if (!cfg->async_out) {
@@ -2463,6 +2552,21 @@ int wcb_generate_prompted(wcb_handle* h, const float* mel, int B, const wcb_gen_
     REQUIRE(prompts && prompt_len, "wcb_generate_prompted: prompts and prompt_len are required (wcb_generate_sampled decodes one shared prompt)");
     GenCall c{mel, B, cfg, nullptr, 1, out_ids, out_steps, stream, bias, bb, out_logprobs, nullptr, smp};
     c.prompts = prompts; c.prompt_ld = prompt_ld; c.prompt_len = prompt_len;
+    generate_impl(h, c);
+  });
+}
+
+int wcb_generate_windows(wcb_handle* h, const wcb_windows* w, int rows, const wcb_gen_cfg* cfg, const wcb_bias* bias,
+                         const wcb_bias_batch* bb, const int32_t* prompts, int prompt_ld, const int32_t* prompt_len,
+                         int32_t* out_ids, float* out_logprobs, float* out_no_speech, int32_t* out_steps, void* stream) {
+  return guarded(h, [&] {
+    REQUIRE(h && cfg && w, "bad argument");
+    REQUIRE(!(bias && bb), "wcb_generate_windows: a shared automaton or a bias batch, not both");
+    REQUIRE(prompts && prompt_len, "wcb_generate_windows: prompts and prompt_len are required (prompt_len 1: the start token alone)");
+    if (cfg->num_beams != 1) throw WcbError(WCB_ERR_UNSUPPORTED, "wcb_generate_windows is greedy only (num_beams = 1)");
+    GenCall c{nullptr, rows, cfg, nullptr, 1, out_ids, out_steps, stream, bias, bb, out_logprobs, nullptr, nullptr};
+    c.prompts = prompts; c.prompt_ld = prompt_ld; c.prompt_len = prompt_len;
+    c.win = w; c.out_no_speech = out_no_speech;
     generate_impl(h, c);
   });
 }
@@ -2570,6 +2674,7 @@ int wcb_decode_step(wcb_handle* h, wcb_state* st, const wcb_bias* bias, int32_t*
       sc.score_out = scores;
       sc.embedded = true;   // (wcb_decode_begin embedded the first input; each finalize embeds the next)
       if (st->logprobs) sc.logprob_out = D.lpbuf.as<float>();
+      if (st->no_speech) sc.nsp_out = D.nsp.as<float>();
       if (st->sampling) sc.samp = D.samp.as<uint64_t>();
       if (st->ragged) sc.pos_off = D.poff.as<int>();
       apply_rules(h, sc);   // (fixed for the whole decode: wcb_set_token_rules is refused while the state is open)
@@ -2664,6 +2769,29 @@ int wcb_decode_enable_logprobs(wcb_handle* h, wcb_state* st) {
     ensure_lp_ws(h, D, st->B, st->max_new);
     HIPCHK(hipMemsetAsync(D.lpbuf.p, 0, (size_t)st->B * st->max_new * 4, D.hs));
     st->logprobs = true;
+  });
+}
+
+int wcb_decode_enable_no_speech(wcb_handle* h, wcb_state* st) {
+  return guarded(h, [&] {
+    DecCtx& D = step_ctx(h, st);
+    if (st->nb > 1) throw WcbError(WCB_ERR_UNSUPPORTED, "the no-speech probability is greedy only (a beam-search state)");
+    if (st->fwd != 0) throw WcbError(WCB_ERR_STATE, "wcb_decode_enable_no_speech on a forward cache (wcb_forward_cached state)");
+    if (st->steps != 0) throw WcbError(WCB_ERR_STATE, "wcb_decode_enable_no_speech: after the first step (right after wcb_decode_begin)");
+    if (!st->logprobs) throw WcbError(WCB_ERR_STATE, "wcb_decode_enable_no_speech: enable the token log-probs first (wcb_decode_enable_logprobs)");
+    D.nsp.ensure((size_t)kWinRows * 4);
+    st->no_speech = true;
+  });
+}
+
+int wcb_decode_no_speech(wcb_handle* h, wcb_state* st, float* out, void* stream) {
+  return guarded(h, [&] {
+    DecCtx& D = step_ctx(h, st, out, "bad argument");
+    if (!st->no_speech) throw WcbError(WCB_ERR_STATE, "wcb_decode_no_speech: off (wcb_decode_enable_no_speech)");
+    if (st->steps < 1) throw WcbError(WCB_ERR_STATE, "wcb_decode_no_speech: before the first step");
+    sync_in(h, stream, D.hs);
+    HIPCHK(hipMemcpyAsync(out, D.nsp.p, (size_t)st->B * 4, hipMemcpyDeviceToDevice, D.hs));
+    sync_out(h, stream, D.hs);
   });
 }
 
@@ -3622,6 +3750,25 @@ int wcb_op_lm_head_rules(int dtype, const void* A, const void* W, int M, int V, 
     select_finalize(s, st);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st));   // the scratch buffers and the pageable host sources live until here
+  });
+}
+
+int wcb_op_window_cut(int dtype, const float* mel, int clips, int n_mel, int T, int T_ld, int rows, const int32_t* clip_idx,
+                      const int32_t* seek, const int32_t* seek_num_frames, void* xt, void* stream) {
+  return guarded(nullptr, [&] {
+    REQUIRE(dtype >= 0 && dtype <= 2 && xt && n_mel >= 1, "bad argument");
+    const wcb_windows w{mel, clips, T, T_ld, clip_idx, seek, seek_num_frames};
+    check_windows(&w, rows);
+    DevBuf ints;
+    ints.ensure((size_t)3 * kWinRows * 4);
+    int v[3 * kWinRows] = {};
+    for (int r = 0; r < rows; ++r) { v[r] = clip_idx[r]; v[kWinRows + r] = seek[r]; v[2 * kWinRows + r] = seek_num_frames[r]; }
+    hipStream_t st = (hipStream_t)stream;
+    write_i32(ints.as<int>(), v, 3 * kWinRows, st);
+    mel_window_to_conv_input((DType)dtype, mel, n_mel, T_ld, ints.as<int>(), ints.as<int>() + kWinRows, ints.as<int>() + 2 * kWinRows,
+                             rows, xt, (long)(kFrames + 2) * n_mel, st);
+    HIPCHK(hipStreamSynchronize(st));
+    ints.release();
   });
 }
 

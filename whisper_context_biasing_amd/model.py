@@ -29,10 +29,11 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import longform as _longform
 from . import prompts as _prompts
 from . import request as _request
-from .config import (FRAME_SECONDS, N_SAMPLES, WhisperDims, dims_from_hf_config, get_dims, parse_segments, timestamp_ids,
-                     words_from_token_times)
+from .config import (FRAME_SECONDS, HOP, N_SAMPLES, WhisperDims, dims_from_hf_config, get_dims, parse_segments,
+                     start_of_prev_token_id, timestamp_ids, words_from_token_times)
 from .request import DecodeRequest, _mix64, clip_seeds, compression_ratio  # noqa: F401  (importable from here, as ever)
 
 _TORCH_DT = {_lib.WCB_BF16: torch.bfloat16, _lib.WCB_F16: torch.float16, _lib.WCB_F32: torch.float32}
@@ -69,6 +70,43 @@ class GenerateOutput:
     # generate(prompt_ids=[[...], ...]) (per-clip prompts): prompt_lengths [B] int64, P_b = len(prompt b) + 1; sequences
     # is then [B, Pmax + n], clip b's prompt left-padded with pad_token_id to Pmax = max P_b (prompts.unpack_prompts)
     prompt_lengths: Optional[torch.Tensor] = None
+    # a long-form window decode (transcribe_long): no_speech_prob [B] f32, softmax(raw logits at the start token)[<|nospeech|>]
+    no_speech_prob: Optional[torch.Tensor] = None
+
+
+@dataclass
+class LongFormOutput:
+    """transcribe_long()'s result. sequences [B, W] int64: every clip's segments' tokens (timestamps included), right-padded
+    with pad_token_id, as HF returns them; segments: per clip a list of (start_s, end_s, token_ids) in absolute seconds;
+    seeks: per clip the window starts in mel frames; no_speech_probs / avg_logprobs: per clip one float per window;
+    window_ids: per clip every window's generated ids (EOS and pads stripped; a skipped window's too)."""
+    sequences: torch.Tensor
+    segments: list
+    seeks: list
+    no_speech_probs: list
+    avg_logprobs: list
+    window_ids: list
+
+
+class _WindowBatch:
+    """The clips of one long-form decode as the library takes them (wcb_windows): long features [clips, n_mel, T_ld] f32 on
+    the device with T valid frames per row, and per decode row its clip, window start and frame count. Sliced by rows like
+    the mel tensor of a short-form call."""
+
+    def __init__(self, feats: torch.Tensor, T: int, clip_idx, seek, frames):
+        self.feats, self.T = feats, int(T)
+        self.clip_idx, self.seek, self.frames = (np.ascontiguousarray(np.asarray(a, dtype=np.int32)) for a in (clip_idx, seek, frames))
+
+    @property
+    def shape(self):
+        return (len(self.clip_idx),)
+
+    def __getitem__(self, rows):
+        return _WindowBatch(self.feats, self.T, self.clip_idx[rows], self.seek[rows], self.frames[rows])
+
+    def abi(self):
+        f = self.feats
+        return _lib.windows(f.data_ptr(), f.shape[0], self.T, f.shape[2], self.clip_idx, self.seek, self.frames)
 
 
 class _PackedPrompts:
@@ -216,6 +254,14 @@ class StepDecoder:
         _lib.check(m._lib.wcb_decode_logprobs(m._h, self._st, _ptr(out), width, C.byref(n), _stream(m.device)), m._h,
                    "wcb_decode_logprobs")
         return out[:, :n.value]
+
+    def no_speech_prob(self):
+        """[B] f32: softmax(raw logits of the first step)[<|nospeech|>] (decode_begin(logprobs=True, no_speech=True)),
+        once a step was taken."""
+        m = self.model
+        out = torch.empty(self.B, dtype=torch.float32, device=m.device)
+        _lib.check(m._lib.wcb_decode_no_speech(m._h, self._st, _ptr(out), _stream(m.device)), m._h, "wcb_decode_no_speech")
+        return out
 
     def close(self):
         if self._st:
@@ -422,6 +468,54 @@ class WhisperCB:
         _lib.check(self._lib.wcb_encode(self._h, _ptr(x), B, _ptr(enc), _stream(self.device)), self._h, "wcb_encode")
         return enc
 
+    def log_mel_long(self, pcm, num_samples=None):
+        """WhisperFeatureExtractor(truncation=False, padding="longest", return_attention_mask=True) equivalent: f32 PCM
+        [B, N] (or [N], or a list of clips of different lengths) -> (mel f32 [B, n_mel, N // 160] on the device, max_frames
+        [B] int64 = the attention mask's sum). `num_samples` [B]: the valid samples of every row (default: the clips' own
+        lengths, N for an array); the samples past them read as zero. The max - 8 clamp is taken over the whole clip."""
+        if isinstance(pcm, (list, tuple)) and len(pcm) and np.ndim(pcm[0]) == 1:
+            if num_samples is None:
+                num_samples = [len(c) for c in pcm]
+            x = torch.zeros(len(pcm), max(len(c) for c in pcm), dtype=torch.float32)
+            for b, c in enumerate(pcm):
+                x[b, :len(c)] = torch.as_tensor(c, dtype=torch.float32)
+        else:
+            x = torch.as_tensor(pcm, dtype=torch.float32)
+            if x.dim() == 1:
+                x = x[None]
+        x = x.to(self.device).contiguous()
+        B, N = x.shape
+        nv = np.full(B, N, dtype=np.int32) if num_samples is None else np.ascontiguousarray(np.asarray(num_samples, dtype=np.int32).reshape(-1))
+        if nv.shape[0] != B:
+            raise ValueError(f"num_samples has {nv.shape[0]} entries, the batch {B} clips")
+        T = N // HOP
+        out = torch.empty(B, self.dims.n_mel, T, dtype=torch.float32, device=self.device)
+        _lib.check(self._lib.wcb_log_mel_long(self._h, _ptr(x), B, nv.ctypes.data, N, N, _ptr(out), T, _stream(self.device)),
+                   self._h, "wcb_log_mel_long")
+        return out, np.minimum((nv.astype(np.int64) + HOP - 1) // HOP, T)   # every 160th sample's flag, as HF rescales the mask
+
+    def encode_windows(self, features, clip_idx, seek, seek_num_frames, num_frames: Optional[int] = None) -> torch.Tensor:
+        """The encoder on windows cut from long features [clips, n_mel, T_ld] f32 (`num_frames` = T valid frames per
+        row, default T_ld): row r = frames [seek[r], seek[r] + seek_num_frames[r]) of clip clip_idx[r], zero-padded to
+        3000 (wcb_encode_windows: the cut writes the conv input directly) -> [rows, 1500, d]."""
+        f = self._long_features(features)
+        wb = _WindowBatch(f, f.shape[2] if num_frames is None else num_frames, clip_idx, seek, seek_num_frames)
+        rows = wb.shape[0]
+        enc = torch.empty(rows, self.dims.n_audio_ctx, self.dims.d_model, dtype=self.torch_dtype, device=self.device)
+        w, keep = wb.abi()
+        _lib.check(self._lib.wcb_encode_windows(self._h, C.byref(w), rows, _ptr(enc), _stream(self.device)), self._h,
+                   "wcb_encode_windows")
+        del keep
+        return enc
+
+    def _long_features(self, features) -> torch.Tensor:
+        x = torch.as_tensor(features)
+        if x.dim() == 2:
+            x = x[None]
+        if x.dim() != 3 or x.shape[1] != self.dims.n_mel or x.shape[2] < 1:
+            raise ValueError(f"expected features [B, {self.dims.n_mel}, T], got {tuple(x.shape)}")
+        return x.to(self.device, torch.float32).contiguous()
+
     # ------------------------------------------------------------------------------ biasing
     @property
     def word_start(self) -> Optional[np.ndarray]:
@@ -621,12 +715,19 @@ class WhisperCB:
         packed = isinstance(prefix, _PackedPrompts)
         pre = None if packed else np.asarray(prefix, dtype=np.int32)
         bb = BiasBatch(self, bias_lists) if bias_lists is not None else None   # per call: not in the automaton LRU
-        head = (self._h, _ptr(x), B, C.byref(cfg))
+        windows = isinstance(x, _WindowBatch)   # long-form: rows cut from long features, the no-speech probability beside the log-probs
+        win, keep_win = x.abi() if windows else (None, None)
+        nsp = torch.zeros(B, dtype=torch.float32, device=self.device) if windows and lp is not None else None
+        head = (self._h, C.byref(win) if windows else _ptr(x), B, C.byref(cfg))
         bias = (bl._h if (bl and not bb) else None, bb._h if bb else None)
         mid = None if packed else (pre.ctypes.data if len(prefix) > 1 else None, len(prefix), _ptr(out))
         scores = (_ptr(lp) if lp is not None else None, _ptr(ss) if ss is not None else None)
         tail = (C.byref(steps), _stream(self.device))
-        if packed:   # per-clip prompts: the greedy family in one entry point
+        if windows:   # (transcribe_long: always per-clip prompts, never sampled)
+            name = "wcb_generate_windows"
+            args = head + bias + (prefix.rows.ctypes.data, prefix.rows.shape[1], prefix.lengths.ctypes.data, _ptr(out)) + scores[:1] + (
+                _ptr(nsp) if nsp is not None else None,) + tail
+        elif packed:   # per-clip prompts: the greedy family in one entry point
             name = "wcb_generate_prompted"
             args = head + (C.byref(smp) if smp is not None else None,) + bias + (
                 prefix.rows.ctypes.data, prefix.rows.shape[1], prefix.lengths.ctypes.data, _ptr(out)) + scores[:1] + tail
@@ -643,7 +744,11 @@ class WhisperCB:
         finally:
             if bb:
                 bb.close()   # the call copied it, as it copied the seeds (also with block=False)
-        return self._generate_result(out, steps.value, prefix, req.block, req.as_dict, lp, ss, req.timestamps)
+        del keep_win
+        res = self._generate_result(out, steps.value, prefix, req.block, req.as_dict, lp, ss, req.timestamps)
+        if nsp is not None:
+            res.no_speech_prob = nsp
+        return res
 
     def _prompt_columns(self, prefix, B: int):
         """(the prompt columns of `sequences`, int64 [B, P]; prompt_lengths [B], None for a shared prefix)."""
@@ -704,6 +809,7 @@ class WhisperCB:
         return GenerateOutput(
             sequences=torch.cat([sot, ids], dim=1), prompt_lengths=plen, token_logprobs=scatter([r.token_logprobs for r in results]),
             avg_logprob=scatter([r.avg_logprob for r in results]), sequences_scores=scatter([r.sequences_scores for r in results]),
+            no_speech_prob=scatter([r.no_speech_prob for r in results]),
             # token rules never meet the fallback (resolve() refuses it): the parts are whole chunks, in order
             segments=[s for r in results for s in r.segments] if req.timestamps else None)
 
@@ -730,11 +836,81 @@ class WhisperCB:
                 break
         return replace(self._join(req, kept), temperatures=torch.from_numpy(used).to(self.device))
 
+    def transcribe_long(self, input_features=None, attention_mask=None, *, pcm=None, num_samples=None, max_new_tokens: int = 224,
+                        condition_on_prev_tokens: bool = False, prompt_ids=None, prompt_condition_type: str = "first-segment",
+                        bias_lists=None, bias_list=None, bias_boost: float = 0.0, suppress_tokens=None,
+                        begin_suppress_tokens=None, max_initial_timestamp: Optional[float] = None,
+                        logprob_threshold: Optional[float] = -1.0, no_speech_threshold: Optional[float] = None,
+                        use_graph: bool = True, temperature=0.0, num_beams: int = 1,
+                        return_token_timestamps: bool = False) -> LongFormOutput:
+        """Long-form transcription: audio of any length, HF `WhisperGenerationMixin.generate`'s long-form branch on this
+        library's greedy path. Input: `input_features` [B, n_mel, T] (the extractor's long mode, T > 3000
+        allowed) with `attention_mask` [B, T] (its sum = the clip's frames; None: T), or `pcm` ([B, N], or a list of clips)
+        with `num_samples`, from which the whole-recording log-mel is computed on the device (log_mel_long).
+
+        Every clip keeps a `seek` in mel frames. While a clip's seek is short of its frames it is active: its next window
+        (at most 3000 frames from seek, zero-padded) is cut on the device straight into the encoder's input, and the
+        active clips are decoded in one greedy batch with the timestamp grammar (`return_timestamps=True`), the caller's
+        `suppress_tokens` / `begin_suppress_tokens` / `max_initial_timestamp`, token log-probs and every clip's own bias
+        list at `bias_boost`; at most `max_new_tokens` tokens per window (capped by n_text_ctx minus the widest prompt).
+        The ids decide the segments and how far seek advances (longform.retrieve_segments). The batch shrinks as clips
+        finish and never reorders; a clip's result does not depend on the clips it is batched with.
+
+        `condition_on_prev_tokens=True`: a window's decoder prompt is <|startofprev|> + the last n_text_ctx // 2 - 1 tokens
+        of the clip's earlier segments (per-clip prompts of different lengths in one batch). `prompt_ids` (one flat prompt)
+        follows HF's `prompt_condition_type`: "first-segment" or "all-segments" (the latter needs conditioning).
+        `no_speech_threshold` (None: off): a window whose avg_logprob < `logprob_threshold` and whose no-speech probability
+        exceeds it is skipped: no segments, seek moves past it.
+
+        Refused with ValueError before any device work: a temperature sequence or `temperature > 0` (the timestamp
+        grammar needs the unperturbed text maximum: no sampling, no temperature fallback inside the loop); `num_beams > 1`;
+        `return_token_timestamps` together with `condition_on_prev_tokens` (the alignment pass takes one shared prefix;
+        without conditioning it is not implemented either and raises NotImplementedError)."""
+        if not self._loaded:
+            raise _lib.WcbError("weights not loaded")
+        _longform.check_args(temperature=temperature, num_beams=num_beams, return_token_timestamps=return_token_timestamps,
+                             condition_on_prev_tokens=condition_on_prev_tokens, prompt_ids=prompt_ids,
+                             prompt_condition_type=prompt_condition_type)
+        if return_token_timestamps:
+            raise NotImplementedError("transcribe_long(return_token_timestamps=True) is not implemented")
+        if (input_features is None) == (pcm is None):
+            raise ValueError("transcribe_long takes input_features or pcm")
+        if pcm is not None:
+            feats, max_frames = self.log_mel_long(pcm, num_samples)
+        else:
+            feats = self._long_features(input_features)
+            if attention_mask is not None and tuple(torch.as_tensor(attention_mask).shape) != (feats.shape[0], feats.shape[2]):
+                raise ValueError(f"attention_mask must be [{feats.shape[0]}, {feats.shape[2]}] like the features")
+            max_frames = (np.full(feats.shape[0], feats.shape[2], dtype=np.int64) if attention_mask is None
+                          else torch.as_tensor(attention_mask).sum(-1).cpu().numpy().astype(np.int64))
+        B, T = feats.shape[0], feats.shape[2]
+        req = _request.resolve(   # every ValueError of the decode arguments, once
+            self.dims, self.generation_config, B, max_length=max_new_tokens, num_beams=1, bias_list=bias_list, bias_boost=bias_boost,
+            bias_lists=bias_lists, prompt_ids=[[] for _ in range(B)], use_graph=use_graph, output_logprobs=True,
+            return_timestamps=True, suppress_tokens=suppress_tokens, begin_suppress_tokens=begin_suppress_tokens,
+            max_initial_timestamp=max_initial_timestamp)
+        st = _longform.LongFormState(
+            max_frames, eos=self.dims.eos_token_id, pad=self.dims.pad_token_id, timestamp_begin=timestamp_ids(self.dims)[0],
+            prev_sot=start_of_prev_token_id(self.dims), n_text_ctx=self.dims.n_text_ctx,
+            condition_on_prev_tokens=condition_on_prev_tokens, prompt_ids=prompt_ids, prompt_condition_type=prompt_condition_type,
+            logprob_threshold=logprob_threshold, no_speech_threshold=no_speech_threshold)
+        while True:
+            active = st.active()
+            if not active:
+                break
+            seek, frames = st.windows(active)
+            sub = replace(req.take(active), prompt=st.prompts(active))
+            res = self._decode(_WindowBatch(feats, T, active, seek, frames), sub)
+            st.update(active, res.sequences[:, sub.prompt_width:].cpu().numpy(), res.avg_logprob.cpu().numpy(),
+                      res.no_speech_prob.cpu().numpy())
+        return LongFormOutput(sequences=torch.from_numpy(st.sequences()).to(self.device), segments=st.segments, seeks=st.seeks,
+                              no_speech_probs=st.no_speech_probs, avg_logprobs=st.avg_logprobs, window_ids=st.window_ids)
+
     def decode_begin(self, encoder_outputs, prompt_ids=None, bias_list=None, bias_boost: float = 0.0,
                      min_new_tokens: int = 0, num_beams: int = 1, max_length: Optional[int] = None,
                      bias_lists=None, logprobs: bool = False, temperature: float = 0.0, seed=0,
                      return_timestamps: bool = False, suppress_tokens=None, begin_suppress_tokens=None,
-                     max_initial_timestamp: Optional[float] = None) -> "StepDecoder":
+                     max_initial_timestamp: Optional[float] = None, no_speech: bool = False) -> "StepDecoder":
         """Step-wise decoding from an encoder output [B, 1500, d] (this model's dtype, on its device): the
         streaming form of generate() (wcb_decode_begin / wcb_decode_begin_beams). Greedy (num_beams = 1) or
         beam search (num_beams 2..8; `max_length` = generate()'s, the beams' length cap: None = the
@@ -749,8 +925,11 @@ class WhisperCB:
         (wcb_decode_enable_sampling; `seed` an int through clip_seeds, or B per-clip seeds); step()'s scores are
         then the winners' perturbed values. `return_timestamps` / `suppress_tokens` / `begin_suppress_tokens` /
         `max_initial_timestamp`: generate()'s token rules for every step of this decode (greedy only; timestamps
-        not with sampling: ValueError)."""
+        not with sampling: ValueError). `no_speech=True` (needs `logprobs=True`: ValueError): StepDecoder.no_speech_prob()
+        gives every clip's no-speech probability after the first step."""
         T, nb = _request.sampling_temperature(temperature), int(num_beams)
+        if no_speech and not logprobs:
+            raise ValueError("no_speech needs logprobs=True (it reuses the log-probs' logsumexp)")
         rules = _request.rules_key(self.dims, return_timestamps, suppress_tokens, begin_suppress_tokens, max_initial_timestamp)
         if rules is not None and nb != 1:
             raise ValueError("suppress_tokens / begin_suppress_tokens / return_timestamps are greedy only: num_beams must be 1")
@@ -799,6 +978,8 @@ class WhisperCB:
         dec = StepDecoder(self, st, B, bl, nb)
         if logprobs:   # greedy only (wcb.h): every step records the log-prob of its token
             _lib.check(self._lib.wcb_decode_enable_logprobs(self._h, st), self._h, "wcb_decode_enable_logprobs")
+        if no_speech:
+            _lib.check(self._lib.wcb_decode_enable_no_speech(self._h, st), self._h, "wcb_decode_enable_no_speech")
         if seeds is not None:
             _lib.check(self._lib.wcb_decode_enable_sampling(self._h, st, T, seeds.ctypes.data_as(C.POINTER(C.c_uint64))),
                        self._h, "wcb_decode_enable_sampling")
