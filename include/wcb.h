@@ -484,6 +484,51 @@ int wcb_decode_no_speech(wcb_handle* h, wcb_state* st, float* out, void* stream)
 int wcb_op_window_cut(int dtype, const float* mel, int clips, int n_mel, int T, int T_ld, int rows, const int32_t* clip_idx,
                       const int32_t* seek, const int32_t* seek_num_frames, void* xt, void* stream);
 
+/* ---- language prompts and per-clip language detection (HF generate(language=, task=) / detect_language; semantics:
+ * DESIGN.md §5h, csrc/k_lang.hip). The language tokens are the ids [lang_begin, lang_begin + n_lang) right after the
+ * decoder start token (Whisper: lang_begin = decoder_start_token_id + 1, n_lang = 99 or 100). Detection is one decoder
+ * pass over [decoder_start] at position 0 on the cross-attention state of the call's own decode context — a greedy
+ * step without selection whose LM head is the language head: f32 logits of the 16-column tiles that cover the range
+ * only, the final LayerNorm fused — then lang_finalize_kernel, one wave per row: columns outside the range and
+ * non-candidates masked, (max, Σexp) and the argmax (lowest index on ties) reduced in a fixed order, so a clip's
+ * result never depends on its batch. No logits leave the chip.
+ * wcb_detect_language: enc = encoder output [B][1500][d] in the model dtype (DEVICE, as wcb_decode_begin's: copied /
+ * projected into the step-wise decode context, so WCB_ERR_STATE while a step-wise decode is open) -> out_ids int32
+ * DEVICE [B] (token ids), out_probs f32 DEVICE [B][n_lang] or NULL (softmax over the candidate languages, 0 elsewhere).
+ * candidates: HOST bitmap of n_lang bits (bit i of word i / 32 = language lang_begin + i may be chosen; copied by
+ * value on the decode stream, free on return) or NULL = every language.
+ * Errors: B outside 1..64, a range that does not lie inside (eos_token_id, vocab) or n_lang outside 1..113:
+ * WCB_ERR_ARG; a candidate bitmap with no bit set: WCB_ERR_ARG. */
+int wcb_detect_language(wcb_handle* h, const void* enc, int B, int lang_begin, int n_lang, const uint32_t* candidates,
+                        int32_t* out_ids, float* out_probs, void* stream);
+/* A language slot in per-clip prompts: every row of `prompts` holds, column_from_end columns before its last one (the
+ * column prompt_ld - 1 - column_from_end, the same for all rows in the right-aligned layout), a language token that the
+ * library fills in on the device: after the encoder the detection pass runs in the decode stream, the finalize stores
+ * every row's id into that column of the context's prompt rows, then the ordinary (ragged) prefill reads them — the
+ * prefill overwrites self-attention slot 0, and the pass advances no per-row decode state (automaton states, timestamp
+ * words, log-prob sums, step and sampling counters). The pass is eager like the prefill; the step graphs are those of
+ * the same call without the slot, so other audio, languages or candidates capture nothing. out_ids (DEVICE [B],
+ * nullable) / out_probs (DEVICE [B][n_lang], nullable) receive what wcb_detect_language writes. */
+typedef struct { int lang_begin, n_lang;
+                 const uint32_t* candidates;     /* HOST bitmap of n_lang bits, NULL: every language */
+                 int column_from_end;            /* >= 0; every prompt_len[b] must be >= column_from_end + 2 */
+                 int32_t* out_ids; float* out_probs; } wcb_lang_cfg;
+/* wcb_generate_prompted / wcb_decode_begin_prompted with the slot (lang = NULL: exactly those). Errors as theirs and
+ * as wcb_detect_language's; a prompt_len[b] < column_from_end + 2: WCB_ERR_ARG; num_beams > 1 with a language slot:
+ * WCB_ERR_UNSUPPORTED. */
+int wcb_generate_lang(wcb_handle*, const float* mel, int B, const wcb_gen_cfg*, const wcb_sample_cfg*, const wcb_bias*,
+                      const wcb_bias_batch*, const int32_t* prompts, int prompt_ld, const int32_t* prompt_len,
+                      const wcb_lang_cfg* lang, int32_t* out_ids, float* out_logprobs, int32_t* out_steps, void* stream);
+int wcb_decode_begin_lang(wcb_handle*, const void* enc, int B, int num_beams, const int32_t* prompts, int prompt_ld,
+                          const int32_t* prompt_len, const wcb_lang_cfg* lang, float bias_boost, int min_new_tokens,
+                          wcb_state** out, void* stream);
+/* The language head and its finalize on caller operands (as wcb_op_lm_head_rules; no LayerNorm): A [M][K], W [V][K] in
+ * dtype (M <= 64, K <= 2560) -> logits f32 DEVICE [M][ld] (ld >= V; only the columns of the 16-column tiles that cover
+ * the range are written, cut at V), out_ids int32 DEVICE [M], out_probs f32 DEVICE [M][n_lang] or NULL; candidates HOST
+ * or NULL. The range must lie inside [0, V). Blocks until done. */
+int wcb_op_lang_head(int dtype, const void* A, const void* W, int M, int V, int K, int lang_begin, int n_lang,
+                     const uint32_t* candidates, int32_t* out_ids, float* out_probs, float* logits, long ld, void* stream);
+
 /* debug counters by name (not part of wcb_profile_read): "graph_captures" = decode graphs instantiated so
  * far on this handle. Unknown name: WCB_ERR_ARG. */
 int wcb_debug_counter(const wcb_handle* h, const char* name, int64_t* out);

@@ -82,6 +82,17 @@ def windows(mel_ptr, clips, T, T_ld, clip_idx, seek, seek_num_frames):
     return w, arrs
 
 
+class WcbLangCfg(C.Structure):
+    _fields_ = [("lang_begin", C.c_int), ("n_lang", C.c_int), ("candidates", C.POINTER(C.c_uint32)),
+                ("column_from_end", C.c_int), ("out_ids", C.c_void_p), ("out_probs", C.c_void_p)]
+
+
+def lang_cfg(lang_begin, n_lang, candidates, column_from_end, out_ids_ptr, out_probs_ptr):
+    """A WcbLangCfg and the candidate bitmap it points into (uint32 words or None; keep both alive for the call)."""
+    cand = candidates.ctypes.data_as(C.POINTER(C.c_uint32)) if candidates is not None else None
+    return WcbLangCfg(int(lang_begin), int(n_lang), cand, int(column_from_end), out_ids_ptr, out_probs_ptr), candidates
+
+
 class WcbTensorView(C.Structure):
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("dtype", C.c_int), ("ndim", C.c_int),
                 ("shape", C.c_int64 * 4), ("stride", C.c_int64 * 4)]
@@ -134,6 +145,12 @@ SIGNATURES = {
     "wcb_generate_prompted": (C.c_int, [_P, _P, C.c_int, C.POINTER(WcbGenCfg), C.POINTER(WcbSampleCfg), _P, _P, _P, C.c_int,
                                         _P, _P, _P, C.POINTER(C.c_int32), _P]),
     "wcb_decode_begin_prompted": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, C.c_float, C.c_int, C.POINTER(_P), _P]),
+    "wcb_detect_language": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
+    "wcb_generate_lang": (C.c_int, [_P, _P, C.c_int, C.POINTER(WcbGenCfg), C.POINTER(WcbSampleCfg), _P, _P, _P, C.c_int,
+                                    _P, C.POINTER(WcbLangCfg), _P, _P, C.POINTER(C.c_int32), _P]),
+    "wcb_decode_begin_lang": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, _P, C.POINTER(WcbLangCfg), C.c_float, C.c_int,
+                                        C.POINTER(_P), _P]),
+    "wcb_op_lang_head": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_long, _P]),
     "wcb_op_attention_decode_window": (C.c_int, [C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P,
                                                  C.c_int, _P]),
     "wcb_log_mel_long": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int64, _P, C.c_int, _P]),

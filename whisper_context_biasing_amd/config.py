@@ -10,6 +10,7 @@ uses eot 50257 / sot 50258 — never hard-code them elsewhere.
 from __future__ import annotations
 
 from dataclasses import dataclass, asdict, replace
+from numbers import Integral
 
 N_AUDIO_CTX = 1500          # encoder positions ([tf] modeling_whisper.py:612-616)
 N_SAMPLES = 480000          # 30 s at 16 kHz ([tf] feature_extraction_whisper.py:91)
@@ -112,6 +113,86 @@ def no_speech_token_id(dims) -> int:
 def start_of_prev_token_id(dims) -> int:
     """<|startofprev|>: two ids before <|notimestamps|> (51864: 50360, 51865: 50361, 51866: 50362)."""
     return timestamp_ids(dims)[1] - 2
+
+
+# Whisper's languages in the order of its tokenizer: <|en|> is decoder_start_token_id + 1, <|zh|> the next id, and so
+# on. The last one, yue, exists only in the 51866 vocabulary (large-v3).
+LANGUAGES = dict((
+    ("en", "english"), ("zh", "chinese"), ("de", "german"), ("es", "spanish"), ("ru", "russian"), ("ko", "korean"),
+    ("fr", "french"), ("ja", "japanese"), ("pt", "portuguese"), ("tr", "turkish"), ("pl", "polish"),
+    ("ca", "catalan"), ("nl", "dutch"), ("ar", "arabic"), ("sv", "swedish"), ("it", "italian"), ("id", "indonesian"),
+    ("hi", "hindi"), ("fi", "finnish"), ("vi", "vietnamese"), ("he", "hebrew"), ("uk", "ukrainian"), ("el", "greek"),
+    ("ms", "malay"), ("cs", "czech"), ("ro", "romanian"), ("da", "danish"), ("hu", "hungarian"), ("ta", "tamil"),
+    ("no", "norwegian"), ("th", "thai"), ("ur", "urdu"), ("hr", "croatian"), ("bg", "bulgarian"),
+    ("lt", "lithuanian"), ("la", "latin"), ("mi", "maori"), ("ml", "malayalam"), ("cy", "welsh"), ("sk", "slovak"),
+    ("te", "telugu"), ("fa", "persian"), ("lv", "latvian"), ("bn", "bengali"), ("sr", "serbian"),
+    ("az", "azerbaijani"), ("sl", "slovenian"), ("kn", "kannada"), ("et", "estonian"), ("mk", "macedonian"),
+    ("br", "breton"), ("eu", "basque"), ("is", "icelandic"), ("hy", "armenian"), ("ne", "nepali"),
+    ("mn", "mongolian"), ("bs", "bosnian"), ("kk", "kazakh"), ("sq", "albanian"), ("sw", "swahili"),
+    ("gl", "galician"), ("mr", "marathi"), ("pa", "punjabi"), ("si", "sinhala"), ("km", "khmer"), ("sn", "shona"),
+    ("yo", "yoruba"), ("so", "somali"), ("af", "afrikaans"), ("oc", "occitan"), ("ka", "georgian"),
+    ("be", "belarusian"), ("tg", "tajik"), ("sd", "sindhi"), ("gu", "gujarati"), ("am", "amharic"),
+    ("yi", "yiddish"), ("lo", "lao"), ("uz", "uzbek"), ("fo", "faroese"), ("ht", "haitian creole"), ("ps", "pashto"),
+    ("tk", "turkmen"), ("nn", "nynorsk"), ("mt", "maltese"), ("sa", "sanskrit"), ("lb", "luxembourgish"),
+    ("my", "myanmar"), ("bo", "tibetan"), ("tl", "tagalog"), ("mg", "malagasy"), ("as", "assamese"), ("tt", "tatar"),
+    ("haw", "hawaiian"), ("ln", "lingala"), ("ha", "hausa"), ("ba", "bashkir"), ("jw", "javanese"),
+    ("su", "sundanese"), ("yue", "cantonese"),
+))
+LANGUAGE_CODES = tuple(LANGUAGES)
+# English name -> code: the names above and the aliases transformers accepts
+TO_LANGUAGE_CODE = {**{name: code for code, name in LANGUAGES.items()},
+                    "burmese": "my", "valencian": "ca", "flemish": "nl", "haitian": "ht", "letzeburgesch": "lb",
+                    "pushto": "ps", "panjabi": "pa", "moldavian": "ro", "moldovan": "ro", "sinhalese": "si",
+                    "castilian": "es", "mandarin": "zh"}
+TASKS = ("translate", "transcribe")
+
+
+def is_multilingual(dims) -> bool:
+    """A multilingual vocabulary: EOS is 50257 (the English-only ones end at 50256 and have no language tokens)."""
+    return dims.eos_token_id == 50257
+
+
+def language_ids(dims):
+    """(lang_begin, n_lang): the language tokens are the n_lang ids from decoder_start_token_id + 1 on, up to the two task
+    tokens (99 for vocab 51865, 100 for 51866)."""
+    lang_begin = dims.decoder_start_token_id + 1
+    return lang_begin, timestamp_ids(dims)[0] - 6 - lang_begin
+
+
+def task_ids(dims) -> dict:
+    """<|translate|> and <|transcribe|>: the ids 7 and 6 before the first timestamp token."""
+    ts0 = timestamp_ids(dims)[0]
+    return {"translate": ts0 - 7, "transcribe": ts0 - 6}
+
+
+def language_token_id(dims, language) -> int:
+    """The token id of one language given as a code ("fr"), an English name ("french"), a token string ("<|fr|>") —
+    case-insensitively, as transformers takes them — or as the token id itself. ValueError for a language Whisper does
+    not know and for one this vocabulary has no token for (yue with 99 languages)."""
+    lang_begin, n_lang = language_ids(dims)
+    if isinstance(language, Integral):
+        t = int(language)
+        if not lang_begin <= t < lang_begin + n_lang:
+            raise ValueError(f"language id {t} outside the language tokens [{lang_begin}, {lang_begin + n_lang})")
+        return t
+    if not isinstance(language, str):
+        raise ValueError(f"language must be a code, a name, a token string or a token id, got {language!r}")
+    name = language.lower()
+    code = name[2:-2] if name.startswith("<|") and name.endswith("|>") else TO_LANGUAGE_CODE.get(name, name)
+    if code not in LANGUAGES:
+        raise ValueError(f"Unsupported language: {language}. Language should be one of: {list(LANGUAGES)} or {list(TO_LANGUAGE_CODE)}.")
+    i = LANGUAGE_CODES.index(code)
+    if i >= n_lang:
+        raise ValueError(f"<|{code}|> is not supported by this model: its vocabulary has {n_lang} language tokens")
+    return lang_begin + i
+
+
+def language_code(dims, token_id: int) -> str:
+    """The language code of a language token id."""
+    lang_begin, n_lang = language_ids(dims)
+    if not lang_begin <= int(token_id) < lang_begin + n_lang:
+        raise ValueError(f"{token_id} is no language token")
+    return LANGUAGE_CODES[int(token_id) - lang_begin]
 
 
 def parse_segments(ids, timestamp_begin, eos=None):

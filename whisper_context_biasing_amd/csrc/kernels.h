@@ -446,6 +446,24 @@ struct DtwArgs {
 size_t dtw_trace_bytes(int m_max, int S_ld);
 void dtw(const DtwArgs& a, int N, hipStream_t s);
 
+// ---- language detection (k_lang.hip; semantics: DESIGN.md §5h)
+constexpr int kLangTiles = 8;      // 16-column tiles over a language range of at most 113 tokens at any alignment (Whisper: 7)
+constexpr int kLangMaxK = 2560;    // widest row the language head normalises in LDS
+constexpr int kLangWords = 4;      // the candidate bitmap: n_lang <= 128 bits
+struct LangArgs {
+  const void* A = nullptr; long lda = 0;                 // rows [M][lda]: f32 residual rows (ln_w non-null) or model-type rows
+  const float* ln_w = nullptr; const float* ln_b = nullptr;   // the final LayerNorm fused into the head (null: none)
+  const void* W = nullptr; int K = 0, M = 0;             // token embedding [V][K] in the model type
+  int lang_begin = 0, n_lang = 0;
+  int col0 = 0, col1 = 0;                                // the columns the head writes: whole tiles around the range, cut at V
+  float* logits = nullptr; long ld = 0;                  // [M][ld] f32, indexed by vocabulary column
+  const uint32_t* cand = nullptr;                        // DEVICE bitmap of n_lang bits (null: every language)
+  int* out_ids = nullptr; float* out_probs = nullptr;    // [M] token ids, [M][n_lang] (each nullable)
+  int* prompts = nullptr; int prompt_ld = 0, prompt_col = 0;   // the device-side prompt rows whose language column is patched (nullable)
+};
+void lang_head(DType t, const LangArgs& a, hipStream_t s);
+void lang_finalize(const LangArgs& a, hipStream_t s);
+
 void fill_i32(int* p, int v, long n, hipStream_t s);
 // dst[0..n) = host values, passed by value in the kernel arguments (stream-ordered, no host buffer
 // lifetime or pageable-copy ordering to worry about)

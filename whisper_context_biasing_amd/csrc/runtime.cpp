@@ -230,6 +230,9 @@ struct DecCtx {
   // no-speech probability (wcb_generate_windows, wcb_decode_enable_no_speech): one float per row [64], written by
   // the scored finalize at step 0; allocated once and never moved (the graphs of such decodes hold its address)
   DevBuf nsp;
+  // language detection (wcb_detect_language, the language slot of wcb_generate_lang / wcb_decode_begin_lang): the
+  // candidate bitmap [kLangWords], written by value on the decode stream at the start of every such call
+  DevBuf lang;
   int* p_stage = nullptr;
   size_t p_stage_words = 0;
   hipEvent_t ev_pcopy = nullptr;
@@ -729,6 +732,7 @@ void wcb_destroy(wcb_handle* h) {
     D.forest.release();
     D.poff.release();
     D.nsp.release();
+    D.lang.release();
     if (D.p_stage) (void)hipHostFree(D.p_stage);
     if (D.ev_pcopy) (void)hipEventDestroy(D.ev_pcopy);
     if (D.f_stage) (void)hipHostFree(D.f_stage);
@@ -2188,6 +2192,73 @@ void decode_prompt(wcb_handle* h, const StepCfg& sc, int P, bool has_prefix) {
   if (sc.nb == 1) step_embed(h, sc);
 }
 
+// Language detection. check_lang: the range and the candidates of a call (V, eos: the vocabulary's);
+// detect_pass: the pass itself in the decode context of sc, on its stream.
+void check_lang(int lang_begin, int n_lang, const uint32_t* cand, int eos, int V) {
+  REQUIRE(n_lang >= 1 && n_lang <= 16 * kLangTiles - 15, "n_lang must be in [1, 113]");
+  REQUIRE(lang_begin > eos && lang_begin <= V - n_lang,
+          "language range [" + std::to_string(lang_begin) + ", " + std::to_string(lang_begin) + " + " + std::to_string(n_lang) +
+              ") outside (eos, vocab)");
+  if (cand) {
+    bool any = false;
+    for (int i = 0; i < n_lang; ++i) any |= (cand[i >> 5] >> (i & 31)) & 1u;
+    REQUIRE(any, "language candidates: the bitmap names no language");
+  }
+}
+// the candidate bitmap into the context (null: none) and the range's tile columns into the arguments
+void lang_range(DecCtx& D, LangArgs& a, int lang_begin, int n_lang, const uint32_t* cand, int V, hipStream_t st) {
+  a.lang_begin = lang_begin; a.n_lang = n_lang;
+  a.col0 = lang_begin / 16 * 16;
+  a.col1 = std::min((lang_begin + n_lang + 15) / 16 * 16, V);
+  if (cand) {
+    D.lang.ensure((size_t)kLangWords * 4);   // once: no call in flight reads it before the first one wrote it
+    int w[kLangWords] = {};
+    std::memcpy(w, cand, (size_t)((n_lang + 31) / 32) * 4);
+    write_i32(D.lang.as<int>(), w, kLangWords, st);
+    a.cand = D.lang.as<uint32_t>();
+  }
+}
+// One decoder pass over [decoder_start] at position 0 for every row of the decode sc begins (its int block zeroed:
+// position 0, nothing generated), the language head on the residual rows in place of the LM head, then the finalize:
+// ids / probabilities out, and with patch_ld > 0 the language column of the context's prompt rows (D.forced
+// [B][patch_ld]) patched. A greedy step without selection: it writes self-attention slot 0 (the prefill writes it
+// again), the step's activations and the `next` ids (decode_prompt sets them again), and advances nothing.
+void detect_pass(wcb_handle* h, const StepCfg& sc, int lang_begin, int n_lang, const uint32_t* cand, int32_t* out_ids,
+                 float* out_probs, int patch_ld, int patch_col) {
+  DecCtx& D = h->dc[sc.buf];
+  StepCfg c = step_cfg(h, sc.buf, sc.B, sc.T, sc.out_ld);
+  c.clips = sc.clips; c.nb = 1; c.xmode = sc.xmode; c.host_pos = 0;
+  const int B = c.B, d = h->d.d_model;
+  fill_i32(RowInts(D, B).next, h->d.decoder_start_token_id, B, D.hs);
+  step_embed(h, c);
+  const int ngrp = (B + h->group_rows - 1) / h->group_rows;   // the row groups of a greedy step, back to back
+  const int ns = std::max(ngrp, std::max(1, std::min(h->n_sub, B)));
+  for (int i = 0; i < ns; ++i) {
+    const int b0 = (int)((long)B * i / ns), b1 = (int)((long)B * (i + 1) / ns);
+    decode_rows(h, c, b0, b1 - b0, i, D.hs);
+  }
+  LangArgs a;
+  a.A = D.dx.as<float>(); a.lda = d; a.ln_w = h->dec_ln_w; a.ln_b = h->dec_ln_b;
+  a.W = h->tok_emb; a.K = d; a.M = B;
+  a.logits = c.logits_out; a.ld = c.logits_ld;
+  lang_range(D, a, lang_begin, n_lang, cand, h->d.vocab, D.hs);
+  a.out_ids = out_ids; a.out_probs = out_probs;
+  if (patch_ld > 0) { a.prompts = D.forced.as<int>(); a.prompt_ld = patch_ld; a.prompt_col = patch_col; }
+  const double cols = a.col1 - a.col0;
+  h->timed("lang_head", 2.0 * B * cols * d, cols * d * esize(h->d.dtype) + (double)B * d * 4, D.hs,
+           [&] { lang_head(h->dt, a, D.hs); });
+  h->timed("lang_finalize", 0, (double)B * cols * 4, D.hs, [&] { lang_finalize(a, D.hs); });
+}
+// the language slot of a prompted call, checked against its prompts (before any device work)
+void check_lang_slot(const wcb_handle* h, const wcb_lang_cfg* L, int prompt_ld, const int32_t* prompt_len, int B, int nb) {
+  if (nb > 1) throw WcbError(WCB_ERR_UNSUPPORTED, "a language slot is greedy only (num_beams = 1): the ragged path");
+  check_lang(L->lang_begin, L->n_lang, L->candidates, h->d.eos_token_id, h->d.vocab);
+  REQUIRE(L->column_from_end >= 0 && L->column_from_end <= prompt_ld - 2, "language slot: column_from_end outside [0, prompt_ld - 2]");
+  for (int b = 0; b < B; ++b)
+    REQUIRE(prompt_len[b] >= L->column_from_end + 2,
+            "language slot: prompt_len[" + std::to_string(b) + "] puts the slot at or before the start token");
+}
+
 // per-utterance lists into decode `st` of context D, before its first step: the forest uploaded, every row in its
 // clip's root state
 void start_forest(wcb_handle* h, DecCtx& D, wcb_state& st, const wcb_bias_batch* bb) {
@@ -2233,6 +2304,8 @@ struct GenCall {
   // long-form (wcb_generate_windows): the B rows are windows of long features (mel is then null), and the no-speech
   // probability of every row [B] (nullable; needs out_logprobs)
   const wcb_windows* win = nullptr; float* out_no_speech = nullptr;
+  // language slot (wcb_generate_lang; with prompts): detected on the device before the prefill
+  const wcb_lang_cfg* lang = nullptr;
 };
 
 // the step-wise decode context, after the check every step-wise entry point makes of its state (`what`: the
@@ -2339,6 +2412,7 @@ static void generate_impl(wcb_handle* h, const GenCall& c) {
       throw WcbError(WCB_ERR_UNSUPPORTED, "the no-speech probability reuses the token log-probs' logsumexp: out_logprobs is required");
     const bool prompted = c.prompts || c.prompt_len;
     if (prompted) check_prompts(c.prompts, c.prompt_ld, c.prompt_len, B, nb);
+    if (c.lang) check_lang_slot(h, c.lang, c.prompt_ld, c.prompt_len, B, nb);
     const int P = prompted ? c.prompt_ld : c.prefix ? c.prefix_len : 1;
     REQUIRE(P >= 1, "prefix_len must be >= 1");
     const int T = P + cfg->max_new_tokens;
@@ -2404,6 +2478,9 @@ static void generate_impl(wcb_handle* h, const GenCall& c) {
     }
     const bool ruled = nb == 1 && h->rules_on;
     if (ruled) apply_rules(h, sc);
+    if (c.lang)   // after the encoder, before the prefill: the pass, then the finalize that patches the prompt rows
+      detect_pass(h, sc, c.lang->lang_begin, c.lang->n_lang, c.lang->candidates, c.lang->out_ids, c.lang->out_probs, P,
+                  P - 1 - c.lang->column_from_end);
     decode_prompt(h, sc, P, c.prefix != nullptr || prompted);
     sc.lm_head = true;
     sc.select = true;
@@ -2582,9 +2659,10 @@ int wcb_generate_windows(wcb_handle* h, const wcb_windows* w, int rows, const wc
 // plen (wcb_decode_begin_prompted): prefix = the per-clip prompts [B][prefix_len] left-padded, plen their lengths
 static void decode_begin(wcb_handle* h, const void* enc, int B, int nb, const int32_t* prefix, int prefix_len,
                          int max_new_tokens, float bias_boost, int min_new_tokens, wcb_state** out, void* stream,
-                         const int32_t* plen = nullptr, bool prompted = false) {
+                         const int32_t* plen = nullptr, bool prompted = false, const wcb_lang_cfg* lang = nullptr) {
   REQUIRE(h && enc && out && B > 0 && B <= 64, "bad argument (1 <= B <= 64, enc and out required)");
   if (prompted) check_prompts(prefix, prefix_len, plen, B, nb);
+  if (lang) check_lang_slot(h, lang, prefix_len, plen, B, nb);
   if (!h->ready) throw WcbError(WCB_ERR_STATE, "weights not finalized");
   if (nb < 1) throw WcbError(WCB_ERR_ARG, "num_beams must be >= 1");
   REQUIRE(nb <= kMaxBeams, "num_beams must be in [2, 8] (greedy: num_beams = 1)");
@@ -2613,6 +2691,7 @@ static void decode_begin(wcb_handle* h, const void* enc, int B, int nb, const in
   // the caller's encoder output [B][1500][d] (model dtype) is copied / projected into owned buffers
   enc_to_ctx(h, ci, enc, B, st->xmode, D.hs, stream);
   const StepCfg sc = decode_start(h, ci, *st, prefix, /*shared=*/false, h->empty_bias.get(), plen);
+  if (lang) detect_pass(h, sc, lang->lang_begin, lang->n_lang, lang->candidates, lang->out_ids, lang->out_probs, P, P - 1 - lang->column_from_end);
   decode_prompt(h, sc, P, prefix != nullptr);
   HIPCHK(hipStreamSynchronize(D.hs));
   h->step_state = st.release();
@@ -2632,6 +2711,51 @@ int wcb_decode_begin_prompted(wcb_handle* h, const void* enc, int B, const int32
   return guarded(h, [&] {   // greedy, to the default length cap as wcb_decode_begin
     decode_begin(h, enc, B, 1, prompts, prompt_ld, h ? h->d.n_text_ctx : 0, bias_boost, min_new_tokens, out, stream, prompt_len,
                  /*prompted=*/true);
+  });
+}
+
+int wcb_decode_begin_lang(wcb_handle* h, const void* enc, int B, int num_beams, const int32_t* prompts, int prompt_ld,
+                          const int32_t* prompt_len, const wcb_lang_cfg* lang, float bias_boost, int min_new_tokens,
+                          wcb_state** out, void* stream) {
+  return guarded(h, [&] {
+    decode_begin(h, enc, B, num_beams, prompts, prompt_ld, h ? h->d.n_text_ctx : 0, bias_boost, min_new_tokens, out, stream,
+                 prompt_len, /*prompted=*/true, lang);
+  });
+}
+
+int wcb_generate_lang(wcb_handle* h, const float* mel, int B, const wcb_gen_cfg* cfg, const wcb_sample_cfg* smp,
+                      const wcb_bias* bias, const wcb_bias_batch* bb, const int32_t* prompts, int prompt_ld,
+                      const int32_t* prompt_len, const wcb_lang_cfg* lang, int32_t* out_ids, float* out_logprobs,
+                      int32_t* out_steps, void* stream) {
+  return guarded(h, [&] {
+    REQUIRE(h && cfg, "bad argument");
+    REQUIRE(!(bias && bb), "wcb_generate_lang: a shared automaton or a bias batch, not both");
+    REQUIRE(prompts && prompt_len, "wcb_generate_lang: prompts and prompt_len are required");
+    GenCall c{mel, B, cfg, nullptr, 1, out_ids, out_steps, stream, bias, bb, out_logprobs, nullptr, smp};
+    c.prompts = prompts; c.prompt_ld = prompt_ld; c.prompt_len = prompt_len; c.lang = lang;
+    generate_impl(h, c);
+  });
+}
+
+// language detection on a given encoder output: the step-wise decode context holds it for the length of the call
+int wcb_detect_language(wcb_handle* h, const void* enc, int B, int lang_begin, int n_lang, const uint32_t* candidates,
+                        int32_t* out_ids, float* out_probs, void* stream) {
+  return guarded(h, [&] {
+    REQUIRE(h && enc && out_ids && B > 0 && B <= 64, "bad argument (1 <= B <= 64, enc and out_ids required)");
+    check_lang(lang_begin, n_lang, candidates, h->d.eos_token_id, h->d.vocab);
+    if (!h->ready) throw WcbError(WCB_ERR_STATE, "weights not finalized");
+    REQUIRE(h->nctx < wcb_handle::kMaxCtx, "language detection needs a free decode context (decode_contexts <= 3)");
+    if (h->step_state) throw WcbError(WCB_ERR_STATE, "a step-wise decode is open on this handle (wcb_decode_end first)");
+    const int ci = wcb_handle::kMaxCtx - 1, T = 2;
+    ensure_dec_ws(h, B, B, T, 1, h->xmode, 0, ci, ci + 1);
+    DecCtx& D = h->dc[ci];
+    sync_in(h, stream, D.hs);
+    enc_to_ctx(h, ci, enc, B, h->xmode, D.hs, stream);
+    HIPCHK(hipMemsetAsync(D.ints.p, 0, RowInts::words(B) * 4, D.hs));
+    StepCfg sc = step_cfg(h, ci, B, T, 1);
+    sc.clips = B;
+    detect_pass(h, sc, lang_begin, n_lang, candidates, out_ids, out_probs, 0, 0);
+    sync_out(h, stream, D.hs);
   });
 }
 
@@ -3549,6 +3673,28 @@ int wcb_op_lm_head_sample(int dtype, const void* A, const void* W, int M, int V,
                           const uint64_t* seeds, int step, float* logits, long ld, float* lse, int32_t* sampled,
                           void* stream) {
   return op_lm_head(dtype, A, W, M, V, K, walkers, logits, ld, lse, sampled, stream, true, temperature, seeds, step);
+}
+
+int wcb_op_lang_head(int dtype, const void* A, const void* W, int M, int V, int K, int lang_begin, int n_lang,
+                     const uint32_t* candidates, int32_t* out_ids, float* out_probs, float* logits, long ld, void* stream) {
+  return guarded(nullptr, [&] {
+    REQUIRE(A && W && logits && out_ids && M > 0 && M <= 64 && V > 0 && K > 0 && K <= kLangMaxK && ld >= V,
+            "bad argument (1 <= M <= 64, 1 <= K <= 2560, ld >= V, every pointer)");
+    REQUIRE(dtype >= WCB_BF16 && dtype <= WCB_F32, "dtype");
+    check_lang(lang_begin, n_lang, candidates, -1, V);
+    hipStream_t st = (hipStream_t)stream;
+    DecCtx scratch;   // (only its candidate words are used)
+    struct Free { DecCtx& D; ~Free() { D.lang.release(); } } free_{scratch};
+    LangArgs a;
+    a.A = A; a.lda = K; a.W = W; a.K = K; a.M = M;
+    a.logits = logits; a.ld = ld;
+    lang_range(scratch, a, lang_begin, n_lang, candidates, V, st);
+    a.out_ids = out_ids; a.out_probs = out_probs;
+    lang_head(DType(dtype), a, st);
+    lang_finalize(a, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));   // the scratch words are freed on return
+  });
 }
 
 int wcb_sample_noise(uint64_t seed, int step, int v0, int n, float* out) {

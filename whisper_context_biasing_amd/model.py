@@ -32,7 +32,7 @@ from . import _lib
 from . import longform as _longform
 from . import prompts as _prompts
 from . import request as _request
-from .config import (FRAME_SECONDS, HOP, N_SAMPLES, WhisperDims, dims_from_hf_config, get_dims, parse_segments,
+from .config import (FRAME_SECONDS, HOP, N_SAMPLES, WhisperDims, dims_from_hf_config, get_dims, language_ids, parse_segments,
                      start_of_prev_token_id, timestamp_ids, words_from_token_times)
 from .request import DecodeRequest, _mix64, clip_seeds, compression_ratio  # noqa: F401  (importable from here, as ever)
 
@@ -72,6 +72,12 @@ class GenerateOutput:
     prompt_lengths: Optional[torch.Tensor] = None
     # a long-form window decode (transcribe_long): no_speech_prob [B] f32, softmax(raw logits at the start token)[<|nospeech|>]
     no_speech_prob: Optional[torch.Tensor] = None
+    # generate(language=...): languages [B] int64, every clip's language token id (given, or with "auto" detected on the
+    # device); with per-clip languages or "auto" the forced tail [language, task(, <|notimestamps|>)] follows the start
+    # token in `sequences` and prompt_lengths [B] = len(prompt b) + 1 + len(tail) (prompts.split_row). language_probs
+    # [B, n_lang] f32 with "auto": the softmax over the (candidate) language tokens
+    languages: Optional[torch.Tensor] = None
+    language_probs: Optional[torch.Tensor] = None
 
 
 @dataclass
@@ -86,6 +92,9 @@ class LongFormOutput:
     no_speech_probs: list
     avg_logprobs: list
     window_ids: list
+    # transcribe_long(language=...): every clip's language token id [B] int64 (with "auto": detected from its first window)
+    languages: Optional[torch.Tensor] = None
+    language_probs: Optional[torch.Tensor] = None
 
 
 class _WindowBatch:
@@ -201,6 +210,7 @@ class StepDecoder:
 
     def __init__(self, model, st, B, bias, num_beams=1):
         self.model, self._st, self.B, self._bias, self.num_beams = model, st, B, bias, num_beams
+        self.languages = self.language_probs = None   # decode_begin(language=...)
 
     def step(self):
         m = self.model
@@ -575,7 +585,7 @@ class WhisperCB:
                  compression_ratio_threshold: Optional[float] = 2.4, return_timestamps: bool = False,
                  suppress_tokens=None, begin_suppress_tokens=None, max_initial_timestamp: Optional[float] = None,
                  return_token_timestamps: bool = False, alignment_heads=None, num_frames=None,
-                 median_filter_width: int = 7, **kwargs):
+                 median_filter_width: int = 7, language=None, task: Optional[str] = None, language_candidates=None, **kwargs):
         """Greedy (num_beams = 1, the reference's eval setting) or HF beam
         search (num_beams = 2..8, [tf] generation/utils.py:3208) on the device.
 
@@ -648,6 +658,20 @@ class WhisperCB:
         clips. Raises ValueError with `num_beams > 1` (beam scores count the prompt), with
         `return_token_timestamps=True` (the alignment pass takes one shared prefix), and when the number of prompts
         is not the number of clips.
+
+        `language` / `task` (multilingual models; HF's arguments): the decoder prompt goes on after the
+        start token with the forced tail [language, task] — `task` "transcribe" (the default) or "translate" — and
+        <|notimestamps|> unless `return_timestamps=True`; clip b's prompt is prompt_b + [start] + tail_b. `language` = a
+        code ("fr"), an English name ("french") or a token string ("<|fr|>"), case-insensitively; a sequence of B of
+        them; or "auto": every clip's language is detected on the device between the encoder and the prefill (one decoder
+        pass over [start], the language head, no logits leave the chip), from `language_candidates` when given. One
+        language for the whole batch is a flat prefix (it works with `num_beams > 1` and `return_token_timestamps`);
+        differing languages or "auto" go through the per-clip prompt path (greedy family only), and every clip decodes as
+        it decodes alone with its language. A GenerateOutput then holds `languages` [B] (token ids) and with "auto"
+        `language_probs` [B, n_lang]; "auto" implies `return_dict_in_generate`. With all three left at None the call is
+        exactly the call without them. ValueError: any of them on an English-only model, `task` without `language`,
+        `language_candidates` without "auto", an unknown language (or one this vocabulary has no token for), a list
+        whose length is not B, differing languages or "auto" with `num_beams > 1` or `return_token_timestamps`.
         """
         if not self._loaded:
             raise _lib.WcbError("weights not loaded")
@@ -662,7 +686,8 @@ class WhisperCB:
             compression_ratio_threshold=compression_ratio_threshold, return_timestamps=return_timestamps,
             suppress_tokens=suppress_tokens, begin_suppress_tokens=begin_suppress_tokens,
             max_initial_timestamp=max_initial_timestamp, return_token_timestamps=return_token_timestamps,
-            alignment_heads=alignment_heads, num_frames=num_frames, median_filter_width=median_filter_width)
+            alignment_heads=alignment_heads, num_frames=num_frames, median_filter_width=median_filter_width,
+            language=language, task=task, language_candidates=language_candidates)
         x = self._features(x)
         res = self._generate_with_fallback(x, req) if req.temperatures is not None else self._decode(x, req)
         if req.align is not None:   # right after the decode: one library call leaves its encoder state to the alignment
@@ -684,6 +709,10 @@ class WhisperCB:
     def _prefix(self, req: DecodeRequest):
         """The decoder prompt of one library call: flat prompt + start token, or per-clip prompts packed at these clips' width."""
         start = self.dims.decoder_start_token_id
+        if req.language is not None:   # the forced tail after the start token; a language still to detect holds <|en|>
+            if req.packed:
+                return _PackedPrompts(*_prompts.pack_rows(req.clip_rows(language_ids(self.dims)[0]), start, self.dims.pad_token_id))
+            return list(req.prompt or []) + [start, int(req.language.ids[0])] + list(req.language.rest)
         if req.per_clip_prompts:
             return _PackedPrompts(*_prompts.pack_prompts(req.prompt, start, self.dims.pad_token_id))
         return list(req.prompt or []) + [start]
@@ -718,19 +747,28 @@ class WhisperCB:
         windows = isinstance(x, _WindowBatch)   # long-form: rows cut from long features, the no-speech probability beside the log-probs
         win, keep_win = x.abi() if windows else (None, None)
         nsp = torch.zeros(B, dtype=torch.float32, device=self.device) if windows and lp is not None else None
+        plan = req.language
+        lang_ids = lang_probs = lcfg = keep_lang = None
+        if plan is not None and plan.auto:   # the language slot: detected on the device, patched into the prompt rows
+            lang_begin, n_lang = language_ids(self.dims)
+            lang_ids = torch.empty(B, dtype=torch.int32, device=self.device)
+            lang_probs = torch.empty(B, n_lang, dtype=torch.float32, device=self.device)
+            lcfg, keep_lang = _lib.lang_cfg(lang_begin, n_lang, _request.candidate_bitmap(self.dims, plan.candidates),
+                                            len(plan.rest), _ptr(lang_ids), _ptr(lang_probs))
         head = (self._h, C.byref(win) if windows else _ptr(x), B, C.byref(cfg))
         bias = (bl._h if (bl and not bb) else None, bb._h if bb else None)
         mid = None if packed else (pre.ctypes.data if len(prefix) > 1 else None, len(prefix), _ptr(out))
         scores = (_ptr(lp) if lp is not None else None, _ptr(ss) if ss is not None else None)
         tail = (C.byref(steps), _stream(self.device))
-        if windows:   # (transcribe_long: always per-clip prompts, never sampled)
+        if windows:   # (transcribe_long: always per-clip prompts, never sampled; its languages are always given)
             name = "wcb_generate_windows"
             args = head + bias + (prefix.rows.ctypes.data, prefix.rows.shape[1], prefix.lengths.ctypes.data, _ptr(out)) + scores[:1] + (
                 _ptr(nsp) if nsp is not None else None,) + tail
-        elif packed:   # per-clip prompts: the greedy family in one entry point
-            name = "wcb_generate_prompted"
+        elif packed:   # per-clip prompts: the greedy family in one entry point (with a language slot: its _lang form)
+            name = "wcb_generate_prompted" if lcfg is None else "wcb_generate_lang"
             args = head + (C.byref(smp) if smp is not None else None,) + bias + (
-                prefix.rows.ctypes.data, prefix.rows.shape[1], prefix.lengths.ctypes.data, _ptr(out)) + scores[:1] + tail
+                prefix.rows.ctypes.data, prefix.rows.shape[1], prefix.lengths.ctypes.data) + (
+                () if lcfg is None else (C.byref(lcfg),)) + (_ptr(out),) + scores[:1] + tail
         elif smp is not None:
             name, args = "wcb_generate_sampled", head + (C.byref(smp),) + bias + mid + scores[:1] + tail
         elif scored:
@@ -744,10 +782,20 @@ class WhisperCB:
         finally:
             if bb:
                 bb.close()   # the call copied it, as it copied the seeds (also with block=False)
-        del keep_win
+        del keep_win, keep_lang
+        if lang_ids is not None and req.block:   # the detected ids into the host copy of the prompt rows (`sequences`)
+            prefix.rows[:, prefix.rows.shape[1] - 1 - len(plan.rest)] = lang_ids.cpu().numpy()
         res = self._generate_result(out, steps.value, prefix, req.block, req.as_dict, lp, ss, req.timestamps)
         if nsp is not None:
             res.no_speech_prob = nsp
+        if plan is not None and (isinstance(res, GenerateOutput) or plan.auto):
+            if not isinstance(res, GenerateOutput):   # block=False: device views, valid after synchronize()
+                res = GenerateOutput(sequences=res)
+            if plan.auto:   # (block=False: the int32 ids the decode stream writes, like the other device views)
+                res.languages = lang_ids.to(torch.int64) if req.block else lang_ids
+            else:
+                res.languages = torch.from_numpy(plan.ids).to(self.device)
+            res.language_probs = lang_probs
         return res
 
     def _prompt_columns(self, prefix, B: int):
@@ -806,7 +854,12 @@ class WhisperCB:
             return scatter(results, pad, torch.int64)
         sot, plen = self._prompt_columns(self._prefix(req), req.B)
         ids = scatter([r.sequences[:, P:] for _, _, r, P in parts], pad, torch.int64)
+        languages = scatter([r.languages for r in results], 0, torch.int64) if req.language is not None else None
+        if languages is not None and req.language.auto:   # the detected ids into the prompt columns packed again
+            sot = sot.clone()
+            sot[:, sot.shape[1] - 1 - len(req.language.rest)] = languages
         return GenerateOutput(
+            languages=languages, language_probs=scatter([r.language_probs for r in results]) if languages is not None else None,
             sequences=torch.cat([sot, ids], dim=1), prompt_lengths=plen, token_logprobs=scatter([r.token_logprobs for r in results]),
             avg_logprob=scatter([r.avg_logprob for r in results]), sequences_scores=scatter([r.sequences_scores for r in results]),
             no_speech_prob=scatter([r.no_speech_prob for r in results]),
@@ -817,7 +870,7 @@ class WhisperCB:
         """generate(temperature=(t0, t1, ...)): HF's generate_with_fallback rule. Attempt i decodes the still-failing
         clips (their mel re-encoded: the rare path pays the encoder again) through _decode, so a failing subset above
         64 clips splits as any batch does; a clip keeps the first attempt it passes, or the last one."""
-        kept, used, todo = [], np.zeros(req.B, dtype=np.float32), np.arange(req.B)
+        kept, used, todo, probs = [], np.zeros(req.B, dtype=np.float32), np.arange(req.B), None
         lpt, crt = req.logprob_threshold, req.compression_ratio_threshold
         for i, T in enumerate(req.temperatures):
             whole = len(todo) == req.B   # then the caller's tensor itself: no gather
@@ -834,7 +887,47 @@ class WhisperCB:
             todo = todo[fail]
             if not len(todo):
                 break
-        return replace(self._join(req, kept), temperatures=torch.from_numpy(used).to(self.device))
+            if req.language is not None and req.language.auto:   # detected on the first attempt: given from now on
+                probs = res.language_probs
+                req = req.with_languages(res.languages.cpu().numpy())
+        out = replace(self._join(req, kept), temperatures=torch.from_numpy(used).to(self.device))
+        if probs is not None:
+            out.language_probs = probs
+        return out
+
+    def detect_language(self, input_features=None, encoder_outputs=None, language_candidates=None, return_probs: bool = False):
+        """HF `detect_language` on the device: every clip's language token id, [B] int64, from `input_features`
+        [B, n_mel, 3000] (encoded here) or `encoder_outputs` [B, 1500, d] — exactly one of them. One decoder pass over
+        [start], the language head over the language tokens only and the argmax, all on the chip (wcb_detect_language);
+        `language_candidates` (codes, names or token strings) restricts the choice. `return_probs=True` also returns
+        [B, n_lang] f32: the softmax over the (candidate) language tokens only, 0 for a language that is no candidate."""
+        if not self._loaded:
+            raise _lib.WcbError("weights not loaded")
+        if input_features is None and encoder_outputs is None:
+            raise ValueError("You have to specify either `input_features` or `encoder_outputs`")
+        if input_features is not None and encoder_outputs is not None:
+            raise ValueError("Make sure to specify only one of `input_features` or `encoder_outputs` - not both!")
+        plan = _request.resolve_language(self.dims, 1, "auto", None, language_candidates)
+        x = self._features(input_features) if input_features is not None else self._encoder_state(encoder_outputs)
+        ids, probs = [], []
+        for i in range(0, x.shape[0], 64):   # 64 clips per library call
+            enc = self.encode(x[i:i + 64]) if input_features is not None else x[i:i + 64]
+            a, b = self._detect(enc, plan.candidates)
+            ids.append(a)
+            probs.append(b)
+        ids = torch.cat(ids).to(torch.int64)
+        return (ids, torch.cat(probs)) if return_probs else ids
+
+    def _detect(self, enc: torch.Tensor, candidates):
+        """wcb_detect_language on at most 64 encoder outputs -> (ids int32 [B], probs f32 [B, n_lang]), on the device."""
+        lang_begin, n_lang = language_ids(self.dims)
+        B = enc.shape[0]
+        ids = torch.empty(B, dtype=torch.int32, device=self.device)
+        probs = torch.empty(B, n_lang, dtype=torch.float32, device=self.device)
+        bits = _request.candidate_bitmap(self.dims, candidates)
+        _lib.check(self._lib.wcb_detect_language(self._h, _ptr(enc), B, lang_begin, n_lang, bits.ctypes.data if bits is not None else None,
+                                                 _ptr(ids), _ptr(probs), _stream(self.device)), self._h, "wcb_detect_language")
+        return ids, probs
 
     def transcribe_long(self, input_features=None, attention_mask=None, *, pcm=None, num_samples=None, max_new_tokens: int = 224,
                         condition_on_prev_tokens: bool = False, prompt_ids=None, prompt_condition_type: str = "first-segment",
@@ -842,7 +935,8 @@ class WhisperCB:
                         begin_suppress_tokens=None, max_initial_timestamp: Optional[float] = None,
                         logprob_threshold: Optional[float] = -1.0, no_speech_threshold: Optional[float] = None,
                         use_graph: bool = True, temperature=0.0, num_beams: int = 1,
-                        return_token_timestamps: bool = False) -> LongFormOutput:
+                        return_token_timestamps: bool = False, language=None, task: Optional[str] = None,
+                        language_candidates=None) -> LongFormOutput:
         """Long-form transcription: audio of any length, HF `WhisperGenerationMixin.generate`'s long-form branch on this
         library's greedy path. Input: `input_features` [B, n_mel, T] (the extractor's long mode, T > 3000
         allowed) with `attention_mask` [B, T] (its sum = the clip's frames; None: T), or `pcm` ([B, N], or a list of clips)
@@ -862,6 +956,12 @@ class WhisperCB:
         `no_speech_threshold` (None: off): a window whose avg_logprob < `logprob_threshold` and whose no-speech probability
         exceeds it is skipped: no segments, seek moves past it.
 
+        `language` / `task` / `language_candidates` as generate() takes them: every window's prompt continues after the
+        start token with [language, task] (long-form always decodes with timestamps, so without <|notimestamps|>). With
+        "auto" every clip's language is detected from its first window (HF), on the device, and every later window of the
+        clip reuses it; `languages` (and `language_probs`) of the result hold it. Not together with `no_speech_threshold`
+        (HF reads the no-speech probability at the start token, which then lies inside the prefill): ValueError.
+
         Refused with ValueError before any device work: a temperature sequence or `temperature > 0` (the timestamp
         grammar needs the unperturbed text maximum: no sampling, no temperature fallback inside the loop); `num_beams > 1`;
         `return_token_timestamps` together with `condition_on_prev_tokens` (the alignment pass takes one shared prefix;
@@ -875,6 +975,13 @@ class WhisperCB:
             raise NotImplementedError("transcribe_long(return_token_timestamps=True) is not implemented")
         if (input_features is None) == (pcm is None):
             raise ValueError("transcribe_long takes input_features or pcm")
+        if language is not None or task is not None or language_candidates is not None:   # before any device work
+            if no_speech_threshold is not None:
+                raise ValueError("language with no_speech_threshold is not supported (the no-speech probability is read at the "
+                                 "start token, which a language prompt puts inside the prefill)")
+            src = pcm if pcm is not None else input_features
+            n_clips = len(src) if isinstance(src, (list, tuple)) else 1 if np.ndim(src) == (1 if pcm is not None else 2) else int(np.shape(src)[0])
+            _request.resolve_language(self.dims, n_clips, language, task, language_candidates, timestamps=True)
         if pcm is not None:
             feats, max_frames = self.log_mel_long(pcm, num_samples)
         else:
@@ -888,7 +995,19 @@ class WhisperCB:
             self.dims, self.generation_config, B, max_length=max_new_tokens, num_beams=1, bias_list=bias_list, bias_boost=bias_boost,
             bias_lists=bias_lists, prompt_ids=[[] for _ in range(B)], use_graph=use_graph, output_logprobs=True,
             return_timestamps=True, suppress_tokens=suppress_tokens, begin_suppress_tokens=begin_suppress_tokens,
-            max_initial_timestamp=max_initial_timestamp)
+            max_initial_timestamp=max_initial_timestamp, language=language, task=task, language_candidates=language_candidates)
+        lang_probs = None
+        if req.language is not None and req.language.auto:   # every clip's language from its first window, then given
+            first = [b for b in range(B) if max_frames[b] > 0]
+            found = np.full(B, language_ids(self.dims)[0], dtype=np.int64)
+            lang_probs = torch.zeros(B, language_ids(self.dims)[1], dtype=torch.float32, device=self.device)
+            if first:
+                frames = [_longform.seek_num_frames(0, int(max_frames[b])) for b in first]
+                enc = self.encode_windows(feats, first, np.zeros(len(first), dtype=np.int64), frames, T)
+                ids, probs = self._detect(enc, req.language.candidates)
+                found[first] = ids.cpu().numpy()
+                lang_probs[torch.as_tensor(first, device=self.device)] = probs
+            req = req.with_languages(found)
         st = _longform.LongFormState(
             max_frames, eos=self.dims.eos_token_id, pad=self.dims.pad_token_id, timestamp_begin=timestamp_ids(self.dims)[0],
             prev_sot=start_of_prev_token_id(self.dims), n_text_ctx=self.dims.n_text_ctx,
@@ -904,13 +1023,16 @@ class WhisperCB:
             st.update(active, res.sequences[:, sub.prompt_width:].cpu().numpy(), res.avg_logprob.cpu().numpy(),
                       res.no_speech_prob.cpu().numpy())
         return LongFormOutput(sequences=torch.from_numpy(st.sequences()).to(self.device), segments=st.segments, seeks=st.seeks,
-                              no_speech_probs=st.no_speech_probs, avg_logprobs=st.avg_logprobs, window_ids=st.window_ids)
+                              no_speech_probs=st.no_speech_probs, avg_logprobs=st.avg_logprobs, window_ids=st.window_ids,
+                              languages=None if req.language is None else torch.from_numpy(req.language.ids).to(self.device),
+                              language_probs=lang_probs)
 
     def decode_begin(self, encoder_outputs, prompt_ids=None, bias_list=None, bias_boost: float = 0.0,
                      min_new_tokens: int = 0, num_beams: int = 1, max_length: Optional[int] = None,
                      bias_lists=None, logprobs: bool = False, temperature: float = 0.0, seed=0,
                      return_timestamps: bool = False, suppress_tokens=None, begin_suppress_tokens=None,
-                     max_initial_timestamp: Optional[float] = None, no_speech: bool = False) -> "StepDecoder":
+                     max_initial_timestamp: Optional[float] = None, no_speech: bool = False, language=None,
+                     task: Optional[str] = None, language_candidates=None) -> "StepDecoder":
         """Step-wise decoding from an encoder output [B, 1500, d] (this model's dtype, on its device): the
         streaming form of generate() (wcb_decode_begin / wcb_decode_begin_beams). Greedy (num_beams = 1) or
         beam search (num_beams 2..8; `max_length` = generate()'s, the beams' length cap: None = the
@@ -926,7 +1048,9 @@ class WhisperCB:
         then the winners' perturbed values. `return_timestamps` / `suppress_tokens` / `begin_suppress_tokens` /
         `max_initial_timestamp`: generate()'s token rules for every step of this decode (greedy only; timestamps
         not with sampling: ValueError). `no_speech=True` (needs `logprobs=True`: ValueError): StepDecoder.no_speech_prob()
-        gives every clip's no-speech probability after the first step."""
+        gives every clip's no-speech probability after the first step. `language` / `task` / `language_candidates`:
+        generate()'s (the forced tail after the start token; "auto" detects on the device before the prefill —
+        wcb_decode_begin_lang); the StepDecoder then has `languages` [B] int64 and, with "auto", `language_probs`."""
         T, nb = _request.sampling_temperature(temperature), int(num_beams)
         if no_speech and not logprobs:
             raise ValueError("no_speech needs logprobs=True (it reuses the log-probs' logsumexp)")
@@ -944,7 +1068,26 @@ class WhisperCB:
         seeds = _request.seed_array(seed, B) if T > 0.0 else None
         start = self.dims.decoder_start_token_id
         packed = None
-        if _prompts.is_nested(prompt_ids) and not isinstance(prompt_ids, np.ndarray):
+        plan = _request.resolve_language(self.dims, B, language, task, language_candidates, timestamps=bool(return_timestamps),
+                                         num_beams=nb)
+        if plan is not None:   # every clip's full decoder prompt: prompt_b + [start] + tail_b
+            if prompt_ids is None:
+                plists = [[] for _ in range(B)]
+            elif _prompts.is_nested(prompt_ids):
+                plists = _prompts.as_lists(prompt_ids)
+            else:
+                plists = [[int(t) for t in prompt_ids]] * B
+            if len(plists) != B:
+                raise ValueError(f"prompt_ids holds {len(plists)} prompts, the batch {B} clips")
+            tails = [[language_ids(self.dims)[0] if plan.ids is None else int(plan.ids[b])] + list(plan.rest) for b in range(B)]
+            if plan.per_clip or len({len(p) for p in plists}) > 1:
+                if nb != 1:
+                    raise ValueError("per-clip prompts of different lengths are greedy only: num_beams must be 1")
+                packed = _PackedPrompts(*_prompts.pack_rows(list(zip(plists, tails)), start, self.dims.pad_token_id))
+                prompt_ids = None
+            else:   # one language, prompts of one length: the dense [B, P] rows, whose last token is the first step's input
+                pre_rows = np.asarray([p + [start] + t for p, t in zip(plists, tails)], dtype=np.int32)
+        elif _prompts.is_nested(prompt_ids) and not isinstance(prompt_ids, np.ndarray):
             plists = _prompts.as_lists(prompt_ids)
             if len(plists) != B:
                 raise ValueError(f"prompt_ids holds {len(plists)} prompts, the batch {B} clips")
@@ -953,7 +1096,9 @@ class WhisperCB:
                     raise ValueError("per-clip prompts of different lengths are greedy only: num_beams must be 1")
                 packed = _PackedPrompts(*_prompts.pack_prompts(plists, start, self.dims.pad_token_id))
             prompt_ids = plists
-        if prompt_ids is None or packed is not None:
+        if plan is not None and packed is None:
+            pre = np.ascontiguousarray(pre_rows)
+        elif prompt_ids is None or packed is not None:
             pre = None
         else:
             p = np.asarray(prompt_ids, dtype=np.int32)
@@ -967,7 +1112,16 @@ class WhisperCB:
         st = C.c_void_p()
         self._install_rules(rules)
         flat = (pre.ctypes.data, pre.shape[1]) if pre is not None else (None, 1)
-        if packed is not None:
+        lang_ids = lang_probs = keep_lang = None
+        if packed is not None and plan is not None and plan.auto:
+            lang_begin, n_lang = language_ids(self.dims)
+            lang_ids = torch.empty(B, dtype=torch.int32, device=self.device)
+            lang_probs = torch.empty(B, n_lang, dtype=torch.float32, device=self.device)
+            lcfg, keep_lang = _lib.lang_cfg(lang_begin, n_lang, _request.candidate_bitmap(self.dims, plan.candidates),
+                                            len(plan.rest), _ptr(lang_ids), _ptr(lang_probs))
+            name, args = "wcb_decode_begin_lang", (1, packed.rows.ctypes.data, packed.rows.shape[1], packed.lengths.ctypes.data,
+                                                   C.byref(lcfg))
+        elif packed is not None:
             name, args = "wcb_decode_begin_prompted", (packed.rows.ctypes.data, packed.rows.shape[1], packed.lengths.ctypes.data)
         elif nb > 1 and max_length is not None:
             name, args = "wcb_decode_begin_beams", (nb,) + flat + (int(max_length),)
@@ -975,7 +1129,11 @@ class WhisperCB:
             name, args = "wcb_decode_begin", (nb,) + flat
         _lib.check(getattr(self._lib, name)(self._h, _ptr(enc), B, *args, float(bias_boost), int(min_new_tokens), C.byref(st),
                                             _stream(self.device)), self._h, name)
+        del keep_lang
         dec = StepDecoder(self, st, B, bl, nb)
+        if plan is not None:
+            dec.languages = lang_ids.to(torch.int64) if plan.auto else torch.from_numpy(plan.ids).to(self.device)
+            dec.language_probs = lang_probs
         if logprobs:   # greedy only (wcb.h): every step records the log-prob of its token
             _lib.check(self._lib.wcb_decode_enable_logprobs(self._h, st), self._h, "wcb_decode_enable_logprobs")
         if no_speech:

@@ -47,6 +47,35 @@ def pack_prompts(prompts: Sequence[Sequence[int]], start_token: int, pad_token: 
     return rows, lens
 
 
+def pack_rows(rows: Sequence[Tuple[Sequence[int], Sequence[int]]], start_token: int, pad_token: int) -> Tuple[np.ndarray, np.ndarray]:
+    """pack_prompts for prompts that go on after the start token (generate(language=...)): rows = B pairs
+    (prompt b, tail b), clip b's decoder prompt being prompt_b + [start_token] + tail_b -> (rows int32 [B, Pmax]
+    left-padded with pad_token, lengths int32 [B] = len(prompt b) + 1 + len(tail b)). The tails of one batch have one
+    length, so they occupy the same last columns in every row. With empty tails it is pack_prompts."""
+    if len(rows) == 0:
+        raise ValueError("prompt_ids: no clips")
+    if len({len(t) for _, t in rows}) != 1:
+        raise ValueError("pack_rows: the tails of one batch must have one length")
+    full = [[int(t) for t in p] + [int(start_token)] + [int(t) for t in tail] for p, tail in rows]
+    lens = np.asarray([len(r) for r in full], dtype=np.int32)
+    P = int(lens.max())
+    out = np.full((len(full), P), int(pad_token), dtype=np.int32)
+    for b, r in enumerate(full):
+        out[b, P - len(r):] = np.asarray(r, dtype=np.int32)
+    return out, lens
+
+
+def split_row(row, length: int, tail_len: int, width: int = None) -> Tuple[List[int], int, List[int]]:
+    """One row of the packed layout (or of generate()'s `sequences`: pass width = Pmax, the prompt columns) with
+    prompt_lengths[b] = `length` and a tail of `tail_len` tokens -> (prompt ids, the start token, tail ids)."""
+    row = [int(t) for t in np.asarray(row).reshape(-1)]
+    P = len(row) if width is None else int(width)
+    if not (0 <= tail_len and tail_len + 1 <= length <= P <= len(row)):
+        raise ValueError("split_row: tail_len + 1 <= length <= width <= len(row) expected")
+    s = P - 1 - tail_len
+    return row[P - length:s], row[s], row[s + 1:P]
+
+
 def unpack_prompts(rows, lengths) -> List[List[int]]:
     """The inverse of pack_prompts on the first Pmax = max(lengths) columns of `rows` (generate()'s `sequences` or the
     packed rows): per clip its prompt ids, without the start token."""

@@ -13,7 +13,7 @@ from typing import Any, List, Optional, Tuple
 import numpy as np
 
 from . import prompts as _prompts
-from .config import TIME_PRECISION, timestamp_ids
+from .config import TIME_PRECISION, TASKS, is_multilingual, language_ids, language_token_id, task_ids, timestamp_ids
 
 _M64 = (1 << 64) - 1
 
@@ -134,6 +134,69 @@ def align_args(dims, B: int, alignment_heads, num_frames, median_filter_width) -
     return dict(heads=heads, num_frames=nf, width=W)
 
 
+@dataclass(frozen=True)
+class LanguagePlan:
+    """What `language=` / `task=` / `language_candidates=` ask of a decode of B clips (resolve_language)."""
+    ids: Optional[np.ndarray]            # int64 [B] language token ids; None with "auto" (the device fills them in)
+    auto: bool                           # detect every clip's language on the device
+    candidates: Optional[Tuple[int, ...]]   # token ids detection may choose from (None: every language)
+    rest: Tuple[int, ...]                # the forced tokens after the language: the task, then <|notimestamps|> or not
+    per_clip: bool                       # differing languages or "auto": the per-clip prompt path
+
+
+def resolve_language(dims, B: int, language=None, task=None, language_candidates=None, *, timestamps: bool = False,
+                     num_beams: int = 1, token_timestamps: bool = False) -> Optional[LanguagePlan]:
+    """The language layer of a call (HF _retrieve_init_tokens: the decoder prompt continues [language, task] after the
+    start token, task defaulting to transcribe, then <|notimestamps|> unless the call decodes with timestamps), or None
+    when none of the three arguments is given. ValueError for what the call cannot mean."""
+    if language is None and task is None and language_candidates is None:
+        return None
+    if not is_multilingual(dims):
+        raise ValueError("language / task / language_candidates need a multilingual model: this vocabulary "
+                         f"(eos {dims.eos_token_id}) has no language tokens")
+    if language is None:
+        raise ValueError("task needs language" if task is not None else 'language_candidates needs language="auto"')
+    if task is not None and task not in TASKS:
+        raise ValueError(f"The `{task}` task is not supported. The task should be one of {list(TASKS)}")
+    auto = isinstance(language, str) and language.lower() == "auto"
+    if language_candidates is not None and not auto:
+        raise ValueError('language_candidates needs language="auto"')
+    ids = cands = None
+    if auto:
+        if language_candidates is not None:
+            cands = tuple(sorted({language_token_id(dims, l) for l in language_candidates}))
+            if not cands:
+                raise ValueError("language_candidates is empty")
+    elif isinstance(language, (list, tuple, np.ndarray)):
+        if len(language) != B:
+            raise ValueError("When passing a list of languages, the length of the list must match the batch size. "
+                             f"Expected length of {B}, but got {len(language)} languages.")
+        ids = np.asarray([language_token_id(dims, l) for l in language], dtype=np.int64)
+    else:
+        ids = np.full(B, language_token_id(dims, language), dtype=np.int64)
+    per_clip = auto or bool((ids != ids[0]).any())
+    if per_clip and num_beams != 1:
+        raise ValueError('differing languages or language="auto" are greedy only: num_beams must be 1 (the ragged path)')
+    if per_clip and token_timestamps:
+        raise ValueError('return_token_timestamps with differing languages or language="auto" is not supported '
+                         "(the alignment pass takes one shared prefix)")
+    rest = (task_ids(dims)[task or "transcribe"],) + (() if timestamps else (timestamp_ids(dims)[1],))
+    return LanguagePlan(ids=ids, auto=auto, candidates=cands, rest=rest, per_clip=per_clip)
+
+
+def candidate_bitmap(dims, candidates) -> Optional[np.ndarray]:
+    """The candidate languages (token ids; None: every language) as the library's bitmap: uint32 words, bit i of word
+    i // 32 = language lang_begin + i."""
+    if candidates is None:
+        return None
+    lang_begin, n_lang = language_ids(dims)
+    bits = np.zeros((n_lang + 31) // 32, dtype=np.uint32)
+    for t in candidates:
+        i = int(t) - lang_begin
+        bits[i >> 5] |= np.uint32(1 << (i & 31))
+    return bits
+
+
 def span_lists(bias_spans, union: bool = False, pad: int = 50256):
     """The collator's padded per-sample spans ([B, N, L] ints; the pad is the literal 50256 whatever the model —
     data_utils/data_collator.py:107-125) with the padding stripped: row b's distinct spans, in first-seen order, are
@@ -196,13 +259,33 @@ class DecodeRequest:
     as_dict: bool = False
     timestamps: bool = False
     align: Optional[dict] = None                  # align_args() when token timestamps are asked for
+    language: Optional[LanguagePlan] = None       # resolve_language() when language= is given (ids: per clip)
+
+    @property
+    def tail_width(self) -> int:
+        """Forced tokens after the start token: the language, the task and <|notimestamps|> (0 without language=)."""
+        return 0 if self.language is None else 1 + len(self.language.rest)
+
+    @property
+    def packed(self) -> bool:
+        """The call goes through the per-clip prompt path: per-clip prompts, differing languages or "auto"."""
+        return self.per_clip_prompts or (self.language is not None and self.language.per_clip)
+
+    def clip_rows(self, placeholder: int) -> List[List[int]]:
+        """Every clip's decoder prompt for the per-clip path: prompt_b + [start] + tail_b, without the start token's id
+        (the caller's: rows[b] = (prompt_b, tail_b)); `placeholder` stands where the device writes a detected language."""
+        prompts = self.prompt if self.per_clip_prompts else [list(self.prompt or ())] * self.B
+        if self.language is None:
+            return [(list(p), []) for p in prompts]
+        L = self.language
+        return [(list(p), [placeholder if L.ids is None else int(L.ids[b])] + list(L.rest)) for b, p in enumerate(prompts)]
 
     @property
     def prompt_width(self) -> int:
-        """Columns of the decoder prompt: the (widest) prompt and the start token."""
+        """Columns of the decoder prompt: the (widest) prompt, the start token and the forced tail."""
         if self.per_clip_prompts:
-            return 1 + max(len(p) for p in self.prompt)
-        return 1 + len(self.prompt or ())
+            return 1 + max(len(p) for p in self.prompt) + self.tail_width
+        return 1 + len(self.prompt or ()) + self.tail_width
 
     def max_new(self, n_text_ctx: int) -> int:
         """HF: max_length + prompt tokens, capped at max_target_positions ([tf] generation_whisper.py:1932-1940)."""
@@ -218,7 +301,13 @@ class DecodeRequest:
         rows = lambda L: None if L is None else [L[b] for b in idx]   # noqa: E731
         return replace(self, B=len(idx), seeds=cut(self.seeds), attempt_seeds=cut(self.attempt_seeds, 1),
                        prompt=rows(self.prompt) if self.per_clip_prompts else self.prompt, bias_lists=rows(self.bias_lists),
-                       align=self.align and dict(self.align, num_frames=cut(self.align["num_frames"])))
+                       align=self.align and dict(self.align, num_frames=cut(self.align["num_frames"])),
+                       language=self.language and replace(self.language, ids=cut(self.language.ids)))
+
+    def with_languages(self, ids) -> "DecodeRequest":
+        """This request with every clip's language given (ids [B]: what an "auto" decode detected): still the per-clip path."""
+        return replace(self, language=replace(self.language, ids=np.asarray(ids, dtype=np.int64).reshape(-1), auto=False,
+                                              candidates=None))
 
     def attempt(self, i: int) -> "DecodeRequest":
         """Attempt i of the temperature fallback: one scored decode of these clips at temperatures[i]."""
@@ -232,7 +321,7 @@ def resolve(dims, generation_config, B: int, *, bias_spans=None, max_length=None
             bias_lists=None, per_utterance_bias=False, output_logprobs=False, temperature=0.0, seed=0, do_sample=None,
             logprob_threshold=-1.0, compression_ratio_threshold=2.4, return_timestamps=False, suppress_tokens=None,
             begin_suppress_tokens=None, max_initial_timestamp=None, return_token_timestamps=False, alignment_heads=None,
-            num_frames=None, median_filter_width=7) -> DecodeRequest:
+            num_frames=None, median_filter_width=7, language=None, task=None, language_candidates=None) -> DecodeRequest:
     """generate()'s arguments for a batch of B clips -> the DecodeRequest, or the ValueError of what the call cannot mean.
     `generation_config` is the effective one (it defaults max_length and num_beams); `bias_spans` as bias_source() takes it."""
     nb = int(num_beams if num_beams is not None else getattr(generation_config, "num_beams", 1) or 1)
@@ -243,6 +332,8 @@ def resolve(dims, generation_config, B: int, *, bias_spans=None, max_length=None
     temps = tuple(sampling_temperature(t) for t in temperature) if fallback else None   # do_sample plays no part then
     T = 0.0 if fallback else sampling_temperature(temperature, do_sample)
     rules = rules_key(dims, return_timestamps, suppress_tokens, begin_suppress_tokens, max_initial_timestamp)
+    lang = resolve_language(dims, B, language, task, language_candidates, timestamps=bool(return_timestamps), num_beams=nb,
+                            token_timestamps=bool(return_token_timestamps))
     for refused, why in (   # what the library, or the host side of the decode, cannot do
             (per_clip and return_token_timestamps,
              "return_token_timestamps with per-clip prompts is not supported (the alignment pass takes one shared prefix)"),
@@ -272,6 +363,8 @@ def resolve(dims, generation_config, B: int, *, bias_spans=None, max_length=None
         prompt=prompt, per_clip_prompts=per_clip, bias_shared=shared, bias_lists=lists, rules=rules,
         scored=bool(output_logprobs), timestamps=bool(return_timestamps),
         align=align_args(dims, B, alignment_heads, num_frames, median_filter_width) if return_token_timestamps else None,
-        as_dict=bool(return_dict_in_generate or output_logprobs or return_timestamps or return_token_timestamps or fallback))
+        as_dict=bool(return_dict_in_generate or output_logprobs or return_timestamps or return_token_timestamps or fallback
+                     or (lang is not None and lang.auto)),   # (a detected language is part of the result)
+        language=lang)
     req.max_new(dims.n_text_ctx)
     return req
