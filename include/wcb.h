@@ -573,6 +573,68 @@ int wcb_op_gemm_kernel(int dtype, const void* A, const void* W, int M, int N, in
 int wcb_op_gemm_ln(int dtype, const float* X, const float* ln_w, const float* ln_b, const float* stats,
                    const void* W, int M, int N, int K, const float* bias, int act, void* out, int out_f32,
                    void* stream);
+/* the decode step's input embedding as decode_step / prefill_step launch it: row r reads token ids[r] (an id outside
+ * [0, V) reads row 0) and position *pos + r % rps, or with pos_off (DEVICE [M / rps], ragged prompts; nullable)
+ * clamp(*pos + r % rps - pos_off[r / rps], 0, n_pos - 1). tok_emb [V][d], pos_emb [n_pos][d] in dtype; ids [M], pos
+ * DEVICE. Without pos_off the position is not clamped: the caller keeps *pos + rps <= n_pos.
+ * -> x f32 [M][d]; optional: x16 [M][d] = T(x); x16fm = the same fragment-major for the lean LayerNorm-fused
+ * projections ([ceil(M / 16)][d / 32][64 lanes][8]: element (r, c) at lane 16·((c % 32) / 8) + r % 16, slot c % 8;
+ * 16-bit, d = 64, 512 .. 5120 of the lean table, else WCB_ERR_UNSUPPORTED; rows >= M are not written); stats
+ * [M][d / st_w][2] = per-st_w-column (Σx, Σx²), st_w 16 or 32. */
+int wcb_op_embed(int dtype, const void* tok_emb, const void* pos_emb, const int32_t* ids, const int32_t* pos,
+                 const int32_t* pos_off, int M, int d, int V, int n_pos, int rps, float* x, void* x16, void* x16fm,
+                 float* stats, int st_w, void* stream);
+
+/* One decode-step projection launch, configured as the decoder's layer loop configures it (runtime.cpp
+ * decode_rows), on caller operands. The caller passes plain tensors; the derived operands — W' = W·diag(γ), u, c
+ * (the folded LayerNorm), the fragment-major weight copies, the W_k,hᵀ repack, x16 = T(x) — are built by the
+ * preparation code wcb_finalize_weights runs. Fragment-major activations and row statistics come from the caller
+ * (wcb_op_embed or a WCB_PROJ_RESID launch write them). 16-bit dtypes, except path WCB_PATH_DEC (f32 too).
+ * kind:
+ *   QKV      LN-fused, columns < n_split -> out [M][n_split], the others -> kv [2][kv_B][H][kv_T][64] (H =
+ *            (N - n_split) / 128) of cache row r / kv_rps at position *pos + r % kv_rps (the caller keeps *pos +
+ *            kv_rps <= kv_T)
+ *   LN_PLAIN out [M][N] = LN(x)·Wᵀ + b;  LN_GELU  the same through erf-GELU (out_fm: written fragment-major for a
+ *            consumer with K = N, path LEAN_FOLD_FM)
+ *   RESID    x f32 [M][N] += A·Wᵀ + b in place, out16 [M][N] = T(x) (required), optional out16_fm, st_out
+ *            ([M][N / 16][2], path DEC) / rst_out ([M][N / 32][2], paths RING_FOLD, WIDE); A = a16 [M][K], or a_fm
+ *   KQ       N = K = d: out [M][H·d], q'_h = W_k,hᵀ q_h of the q rows a16 [M][d], Wk = cross k_proj.weight [d][d]
+ *   XQK      N = K = d: the LN-fused q projection (W, bias) and KQ in one launch: out [M][H·d] only
+ * path (M <= 64): DEC the general decode GEMM, LEAN the lean kernel, LEAN_FOLD with the LayerNorm folded into the
+ *   weights, LEAN_FOLD_FM with fragment-major activations as well (a_fm in; out_fm / out16_fm out); RESID and KQ
+ *   have no LayerNorm: on the two folded paths they are the lean launch;
+ *   (M > 64): LN_RING a LayerNorm launch then the LDS-ring tile, RING_FOLD the ring tile with the folded LayerNorm
+ *   (rst_in required; rst_out on RESID), WIDE the wide single-burst tiles (12; LN_GELU 22) with the same.
+ * A (kind, path, shape) the path's launcher does not cover is WCB_ERR_UNSUPPORTED: nothing falls back. *taken
+ * (HOST, nullable) receives the launcher that ran (1 lean, 2 fused cross query, 3 decode GEMM, 4 skinny, 5 + 256·t
+ * ring tile (t = 1: 64x64, 2: 64x32, 3: 32x32), 6 wide tile, 7 two-stage tile). u_out / c_out (f32 [N]) and wg_out
+ * ([N][K], dtype) receive the folded operands when non-NULL. Blocks until done (it owns the derived operands). */
+enum wcb_proj_kind { WCB_PROJ_QKV = 0, WCB_PROJ_LN_PLAIN = 1, WCB_PROJ_LN_GELU = 2, WCB_PROJ_RESID = 3, WCB_PROJ_KQ = 4,
+                     WCB_PROJ_XQK = 5 };
+enum wcb_proj_path { WCB_PATH_DEC = 0, WCB_PATH_LEAN = 1, WCB_PATH_LEAN_FOLD = 2, WCB_PATH_LEAN_FOLD_FM = 3,
+                     WCB_PATH_LN_RING = 4, WCB_PATH_RING_FOLD = 5, WCB_PATH_WIDE = 6 };
+typedef struct {
+  int kind, path, dtype;
+  int M, N, K;
+  const float* ln_w; const float* ln_b;   /* γ, β [K] (LN kinds, XQK) */
+  const void* W; const float* bias;       /* W [N][K] (HF layout) in dtype, bias f32 [N] */
+  const void* Wk;                         /* KQ, XQK: encoder_attn.k_proj.weight [d][d] in dtype */
+  float* x;                               /* LN kinds, XQK: f32 rows [M][K]; RESID: [M][N], updated in place */
+  const void* a16;                        /* LN kinds, XQK: T(x) [M][K] (NULL: derived); RESID, KQ: the A rows */
+  const void* a_fm;                       /* LEAN_FOLD_FM: A fragment-major; whole row blocks are read: allocate
+                                             M rounded up to 32 rows (N >= 2048 LN-fused launches take 32-row workgroups) */
+  void* out; int out_fm;
+  void* out16; void* out16_fm;            /* RESID */
+  const float* st_in; float* st_out;      /* per-16-column (Σx, Σx²): the older skinny consumers */
+  const float* rst_in; float* rst_out;    /* per-32-column (Σx, Σx²): the folded ring / wide tiles */
+  void* kv; const int32_t* pos; int kv_B, kv_T, kv_rps, n_split;   /* QKV */
+  int ring_kt;                            /* M > 64: 1 or 2 (0: 1) */
+  int xqk_nch;                            /* XQK: 2, 4, 8, 16 (0: 8) */
+  float* u_out; float* c_out; void* wg_out;
+  int32_t* taken;
+} wcb_dec_proj;
+int wcb_op_dec_proj(const wcb_dec_proj* p, void* stream);
+
 /* the greedy LM head with its softmax partials, then the partial merge (no LayerNorm, no boost, no EOS mask):
  * A [M][K], W [V][K] in dtype (M <= 64) → logits f32 [M][ld] (ld >= V), lse[M] = logsumexp of each logits row,
  * argmax[M] (lowest index on ties). Runs the kernels the decode step runs for that dtype / K / M: the column

@@ -93,6 +93,24 @@ def lang_cfg(lang_begin, n_lang, candidates, column_from_end, out_ids_ptr, out_p
     return WcbLangCfg(int(lang_begin), int(n_lang), cand, int(column_from_end), out_ids_ptr, out_probs_ptr), candidates
 
 
+PROJ_QKV, PROJ_LN_PLAIN, PROJ_LN_GELU, PROJ_RESID, PROJ_KQ, PROJ_XQK = range(6)
+PATH_DEC, PATH_LEAN, PATH_LEAN_FOLD, PATH_LEAN_FOLD_FM, PATH_LN_RING, PATH_RING_FOLD, PATH_WIDE = range(7)
+# GemmTaken of csrc/kernels.h (the low byte of wcb_dec_proj.taken; ring tiles: + 256 · tile)
+TAKEN_LEAN, TAKEN_XQK, TAKEN_DEC_MF, TAKEN_SKINNY, TAKEN_RING_DEC, TAKEN_WIDE, TAKEN_TILE = range(1, 8)
+
+
+class WcbDecProj(C.Structure):
+    """wcb_dec_proj (include/wcb.h), field for field."""
+    _fields_ = [("kind", C.c_int), ("path", C.c_int), ("dtype", C.c_int), ("M", C.c_int), ("N", C.c_int), ("K", C.c_int),
+                ("ln_w", C.c_void_p), ("ln_b", C.c_void_p), ("W", C.c_void_p), ("bias", C.c_void_p), ("Wk", C.c_void_p),
+                ("x", C.c_void_p), ("a16", C.c_void_p), ("a_fm", C.c_void_p), ("out", C.c_void_p), ("out_fm", C.c_int),
+                ("out16", C.c_void_p), ("out16_fm", C.c_void_p), ("st_in", C.c_void_p), ("st_out", C.c_void_p),
+                ("rst_in", C.c_void_p), ("rst_out", C.c_void_p), ("kv", C.c_void_p), ("pos", C.c_void_p),
+                ("kv_B", C.c_int), ("kv_T", C.c_int), ("kv_rps", C.c_int), ("n_split", C.c_int), ("ring_kt", C.c_int),
+                ("xqk_nch", C.c_int), ("u_out", C.c_void_p), ("c_out", C.c_void_p), ("wg_out", C.c_void_p),
+                ("taken", C.POINTER(C.c_int32))]
+
+
 class WcbTensorView(C.Structure):
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("dtype", C.c_int), ("ndim", C.c_int),
                 ("shape", C.c_int64 * 4), ("stride", C.c_int64 * 4)]
@@ -182,6 +200,9 @@ SIGNATURES = {
                                      C.c_int, C.c_int, _P]),
     "wcb_op_gemm_ln": (C.c_int, [C.c_int, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P,
                                  C.c_int, _P]),
+    "wcb_op_embed": (C.c_int, [C.c_int, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P,
+                               C.c_int, _P]),
+    "wcb_op_dec_proj": (C.c_int, [C.POINTER(WcbDecProj), _P]),
     "wcb_op_weighted_ce": (C.c_int, [_P, C.c_long, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_int,
                                      C.c_float, _P, _P, _P, _P]),
     "wcb_wer_counts": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_int,

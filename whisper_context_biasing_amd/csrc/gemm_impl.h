@@ -2502,17 +2502,20 @@ static void gemm_t(const GemmArgs& g, hipStream_t s) {
     throw std::runtime_error("internal error: sampling on a launch that is not the greedy LM head");
   if ((g.sel_deny || g.sel_deny0) && (!g.sel_val || g.tile || g.M > 64))
     throw std::runtime_error("internal error: token rules on a launch that is not the greedy LM head");
+  auto took = [&](int v) { if (g.taken) *g.taken = v; };   // host side only: which launcher ran
+  took(kTakenNone);
   if (g.tile) {   // decoder rows > 64 (beams, prefill): MFMA tiles, each weight tile read once per 64-128 rows
     if constexpr (sizeof(T) == 2) {
       // tile 2 (192+ rows, the d-wide and wide projections): 64-row tiles over a deep LDS-DMA ring, so
       // that even N = d_model spreads over 80-320 workgroups (C3: 320 rows = 5 row tiles); 64 columns
       // where that still fills the chip, else 32. Run-time epilogue (KV append, 16-bit residual copy).
-      if (g.tile == 2 && g.wide && launch_wide<T>(g, g.wide, s)) return;
+      if (g.tile == 2 && g.wide && launch_wide<T>(g, g.wide, s)) { took(kTakenWide); return; }
       if (g.tile == 2 && g.K % 64 == 0 && !g.st_out && g.mode != 1 && !g.addrow &&
           (!g.ln_u || (g.K <= kLnfMaxK && g.rst_in && g.rst_nb * 32 == g.K))) {
         const int mt = (g.M + 63) / 64;
         const bool lnf = g.ln_u != nullptr;
         const bool kt2 = g.ring_kt == 2 && g.K % 128 == 0;           // 128-deep stages
+        took(kTakenRingDec + 256 * (g.N % 64 == 0 && mt * (g.N / 64) >= 240 ? 1 : mt * ((g.N + 31) / 32) >= 240 ? 2 : 3));
         if (g.N % 64 == 0 && mt * (g.N / 64) >= 240) {
           // (128-deep stages measured slower here: C3 4,871 vs 4,946 audio-s/s with all three tiles)
           if (lnf) launch_ring_dec<T, 64, 64, 4, true>(g, s);
@@ -2531,6 +2534,7 @@ static void gemm_t(const GemmArgs& g, hipStream_t s) {
         return;
       }
     }
+    took(kTakenTile);
     if (g.N % 128 == 0) launch_tile<T, 128, 128, 2, 2>(g, s);
     else launch_tile<T, 128, 64, 2, 2>(g, s);
     return;
@@ -2541,19 +2545,19 @@ static void gemm_t(const GemmArgs& g, hipStream_t s) {
     // vocabulary persistently with 32-row workgroups, reading every weight tile once
     if (g.xqk_wk) {   // the fused cross query: the runtime sets it only where dec_xqk_kernel covers the launch
       if (launch_xqk<T>(g.ln_a16, g.a_fm != 0, g.ln_wg_fm, g.ln_u, g.ln_c, g.xqk_wk, g.xqk_out, g.M, g.hs_H, g.K, s,
-                        g.xqk_nch > 0 ? g.xqk_nch : 8)) return;
+                        g.xqk_nch > 0 ? g.xqk_nch : 8)) { took(kTakenXqk); return; }
       throw std::runtime_error("internal error: fused cross query on a launch dec_xqk_kernel does not cover (M " +
                                std::to_string(g.M) + ", H " + std::to_string(g.hs_H) + ", K " + std::to_string(g.K) +
                                ", operands " + std::to_string(!!g.ln_a16) + std::to_string(!!g.ln_wg_fm) +
                                std::to_string(!!g.ln_u) + std::to_string(!!g.ln_c) + std::to_string(!!g.xqk_out) + ")");
     }
-    if (g.lean && launch_lean<T>(g, s)) return;
+    if (g.lean && launch_lean<T>(g, s)) { took(kTakenLean); return; }
     if (g.kq_w) throw std::runtime_error("internal error: fused cross-query on a launch the lean kernel does not cover");
     if (g.a_fm || g.c_fm || g.out16_fm)   // the runtime pairs fragment-major operands only where the lean path takes both
       throw std::runtime_error("internal error: fragment-major operand on a launch the lean kernel does not cover");
     const bool mf1 = (g.M <= 64 && !(g.sel_val && g.M > 16)) || g.K >= 4096;
     const bool ok = mf1 ? launch_dec_mf<T, 1>(g, s) : launch_dec_mf<T, 2>(g, s);
-    if (ok) return;
+    if (ok) { took(kTakenDecMf); return; }
   }
   if (g.M <= 64 || g.mode == 2 || g.ln_w || g.skinny) {
     // rows per workgroup: up to 16·sk_mf; larger M is split over grid.y (more workgroups, less A
@@ -2571,6 +2575,7 @@ static void gemm_t(const GemmArgs& g, hipStream_t s) {
     else if (mf == 2) ok = launch_skinny_mf<T, 2, 1>(g, s);
     else ok = launch_skinny_mf<T, 4, 1>(g, s);
     if (!ok) fprintf(stderr, "wcb: no skinny GEMM instance for K=%d\n", g.K);
+    else took(kTakenSkinny);
     return;
   }
   // 16-bit encoder-size GEMMs: the LDS-ring kernel, 256x256 (2 stages) when N allows it (measured
@@ -2581,8 +2586,9 @@ static void gemm_t(const GemmArgs& g, hipStream_t s) {
   // d-wide out / fc2 (M = 48000, N = 768: 564 tiles = 2.2 rounds against 752 = 2.9), 12 % / 10 %
   // faster (tools/enc_gemm_bench.hip); QKV / fc1 keep 256x256 (192 measured 9 / 15 % slower)
   if constexpr (sizeof(T) == 2) {
-    if (g.pp && launch_pp<T>(g, s)) return;
+    if (g.pp && launch_pp<T>(g, s)) { took(kTakenPp); return; }
     if (g.N % 128 == 0 && g.M >= 4096) {
+      took(kTakenRing);
       const long tm = (g.M + 255) / 256;
       const long r256 = (tm * ((g.N + 255) / 256) + 255) / 256, r192 = (tm * ((g.N + 191) / 192) + 255) / 256;
       if (g.N % 192 == 0 && r192 * 192 * 10 < r256 * 256 * 9) launch_ring<T, 256, 192, 2, 4, 2>(g, s);
@@ -2591,6 +2597,7 @@ static void gemm_t(const GemmArgs& g, hipStream_t s) {
       return;
     }
   }
+  took(kTakenTile);
   if (g.N % 128 == 0) launch_tile<T, 128, 128, 2, 2>(g, s);
   else launch_tile<T, 128, 64, 2, 2>(g, s);
 }

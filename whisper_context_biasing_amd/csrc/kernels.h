@@ -142,7 +142,13 @@ struct GemmArgs {
   // partials still take the raw value). sel_deny0, when non-null, replaces sel_deny at step 0 (*sel_step == 0).
   // A run-time, wave-uniform null check: no instantiation of its own
   const uint32_t* sel_deny = nullptr; const uint32_t* sel_deny0 = nullptr;
+  // HOST pointer (nullable, never read on the device): the launcher gemm() took for this call, a GemmTaken value
+  // (+ 256·detail for the ring tiles: 1 = 64x64, 2 = 64x32, 3 = 32x32). The kernel-level entry points report it;
+  // the runtime leaves it null
+  int* taken = nullptr;
 };
+enum GemmTaken : int { kTakenNone = 0, kTakenLean = 1, kTakenXqk = 2, kTakenDecMf = 3, kTakenSkinny = 4, kTakenRingDec = 5,
+                       kTakenWide = 6, kTakenTile = 7, kTakenRing = 8, kTakenPp = 9 };
 
 void gemm(DType t, const GemmArgs& g, hipStream_t s);
 constexpr int kLnfMaxK = 1280;   // widest K of the ring tiles' folded LayerNorm (GemmArgs::ln_wg)

@@ -3606,6 +3606,211 @@ int wcb_op_gemm_ln(int dtype, const float* X, const float* ln_w, const float* ln
   });
 }
 
+int wcb_op_embed(int dtype, const void* tok_emb, const void* pos_emb, const int32_t* ids, const int32_t* pos,
+                 const int32_t* pos_off, int M, int d, int V, int n_pos, int rps, float* x, void* x16, void* x16fm,
+                 float* stats, int st_w, void* stream) {
+  return guarded(nullptr, [&] {
+    REQUIRE(tok_emb && pos_emb && ids && pos && x, "bad argument (tables, ids, pos and x are required)");
+    REQUIRE(dtype >= WCB_BF16 && dtype <= WCB_F32, "dtype");
+    REQUIRE(M > 0 && d > 0 && V > 0 && n_pos > 0 && rps >= 1 && M % rps == 0, "bad shape (M a multiple of rps)");
+    REQUIRE(!stats || ((st_w == 16 || st_w == 32) && d % st_w == 0), "stats: st_w 16 or 32, d a multiple of it");
+    int nw = 0, kpw = 0;
+    if (x16fm && (dtype == WCB_F32 || !lean_cfg(d, nw, kpw)))
+      throw WcbError(WCB_ERR_UNSUPPORTED, "x16fm: 16-bit, d in the lean table (64, 512 .. 5120)");
+    // step_embed / prefill_step: the same call, the caller's buffers in place of the decode context's
+    embed(DType(dtype), tok_emb, pos_emb, ids, pos, x, stats, M, d, (hipStream_t)stream, x16, V, rps, stats ? st_w : 16,
+          x16fm, pos_off, n_pos);
+    HIPCHK(hipGetLastError());
+  });
+}
+
+// One projection launch of decode_rows() on caller operands. The GemmArgs fields are the ones decode_rows() sets
+// for the kind (QKV: the "dec_qkv" block; LN_PLAIN / XQK: "dec_xq"; LN_GELU: "dec_fc1"; RESID: "dec_out" / "dec_xo" /
+// "dec_fc2"; KQ: "dec_kq"), then the ones its proj() lambda sets for the row count (> 64 rows: the fold / LayerNorm
+// launch / tile / wide block; <= 64: lean, lean_fold); the derived operands are built as wcb_finalize_weights
+// builds them (its fold and fm lambdas, the W_kt repack).
+int wcb_op_dec_proj(const wcb_dec_proj* p, void* stream) {
+  return guarded(nullptr, [&] {
+    REQUIRE(p, "null descriptor");
+    const int kind = p->kind, path = p->path, M = p->M, N = p->N, K = p->K;
+    REQUIRE(kind >= WCB_PROJ_QKV && kind <= WCB_PROJ_XQK, "kind");
+    REQUIRE(path >= WCB_PATH_DEC && path <= WCB_PATH_WIDE, "path");
+    REQUIRE(p->dtype >= WCB_BF16 && p->dtype <= WCB_F32, "dtype");
+    REQUIRE(M > 0 && N > 0 && K > 0 && N % 16 == 0 && K % 64 == 0 && M <= 4096, "bad shape (N % 16, K % 64, M <= 4096)");
+    const bool ln = kind == WCB_PROJ_QKV || kind == WCB_PROJ_LN_PLAIN || kind == WCB_PROJ_LN_GELU || kind == WCB_PROJ_XQK;
+    const bool kq = kind == WCB_PROJ_KQ || kind == WCB_PROJ_XQK;
+    if (ln) REQUIRE(p->ln_w && p->ln_b && p->W && p->bias && p->x && p->out, "LN kinds: ln_w, ln_b, W, bias, x and out");
+    if (kq) REQUIRE(p->Wk && p->out && N == K, "KQ / XQK: Wk and out, N = K = d_model");
+    if (kind == WCB_PROJ_KQ) REQUIRE(p->a16, "KQ: the q rows (a16)");
+    if (kind == WCB_PROJ_RESID)
+      REQUIRE(p->W && p->bias && p->x && p->out16 && (p->a16 || p->a_fm), "RESID: W, bias, x, out16 and the A rows");
+    const int rps = p->kv_rps > 1 ? p->kv_rps : 1;
+    int H = 0;
+    if (kind == WCB_PROJ_QKV) {
+      REQUIRE(p->kv && p->pos && p->kv_B > 0 && p->kv_T > 0, "QKV: kv, pos, kv_B and kv_T");
+      REQUIRE(p->n_split > 0 && p->n_split % 64 == 0 && p->n_split < N && (N - p->n_split) % 128 == 0,
+              "QKV: n_split a multiple of 64, K and V of whole 64-wide heads after it");
+      REQUIRE(M % rps == 0 && M / rps <= p->kv_B && rps <= p->kv_T, "QKV: M / kv_rps cache rows within kv_B");
+      H = (N - p->n_split) / 128;
+    }
+    REQUIRE(p->ring_kt >= 0 && p->ring_kt <= 2, "ring_kt: 1 or 2");
+    REQUIRE(p->xqk_nch == 0 || p->xqk_nch == 2 || p->xqk_nch == 4 || p->xqk_nch == 8 || p->xqk_nch == 16, "xqk_nch");
+    // ---- what the path is defined for
+    const bool lean = path >= WCB_PATH_LEAN && path <= WCB_PATH_LEAN_FOLD_FM;
+    const bool fold = path == WCB_PATH_LEAN_FOLD || path == WCB_PATH_LEAN_FOLD_FM;
+    const bool fm = path == WCB_PATH_LEAN_FOLD_FM;
+    const bool tiled = path >= WCB_PATH_LN_RING;
+    const bool tfold = path == WCB_PATH_RING_FOLD || path == WCB_PATH_WIDE;
+    auto unsupported = [](const std::string& m) { throw WcbError(WCB_ERR_UNSUPPORTED, m); };
+    if (p->dtype == WCB_F32 && (path != WCB_PATH_DEC || kq)) unsupported("f32: path DEC, no cross-query kinds");
+    if (tiled ? (M <= 64 || kind == WCB_PROJ_KQ || kind == WCB_PROJ_XQK) : (M > 64 && kind != WCB_PROJ_KQ))
+      unsupported("paths DEC / LEAN*: M <= 64 (KQ on DEC: any M); tile paths: M > 64, not KQ / XQK");
+    if (lean && M > 64) unsupported("lean paths: M <= 64");
+    const bool lnk = K == 512 || K == 768 || K == 1024 || K == 1280;
+    if (lean && ln && !lnk) unsupported("lean LN-fused projections: K 512, 768, 1024, 1280");
+    if (lean && kind == WCB_PROJ_RESID && !lnk && K != 2048 && K != 3072 && K != 4096 && K != 5120)
+      unsupported("lean residual writers: K 512 .. 5120 of the lean table");
+    // (RESID and KQ have no LayerNorm: on the folded lean paths they are the lean launch, as in decode_rows())
+    if (kind == WCB_PROJ_XQK && !fold) unsupported("XQK: the folded lean paths");
+    if (kind == WCB_PROJ_QKV && lean && rps > 1) unsupported("lean QKV: one position per row");
+    if (kind == WCB_PROJ_QKV && path == WCB_PATH_WIDE) unsupported("QKV keeps the ring tiles");
+    if (tfold && ln && (K > kLnfMaxK || K % 32)) unsupported("folded tiles: K <= 1280");
+    if (path == WCB_PATH_WIDE && (K != 768 && K != 1024 && K != 1280)) unsupported("wide tiles: K 768, 1024, 1280");
+    if (path == WCB_PATH_WIDE && kind == WCB_PROJ_RESID && N != K) unsupported("wide residual writers: N = K = d_model");
+    if (p->st_out && (path != WCB_PATH_DEC || kind != WCB_PROJ_RESID)) unsupported("st_out: RESID on path DEC");
+    if (p->rst_out && !(tfold && kind == WCB_PROJ_RESID && N % 32 == 0)) unsupported("rst_out: RESID on RING_FOLD / WIDE");
+    if (p->out16_fm && !(fm && kind == WCB_PROJ_RESID && (N == 512 || N == 768 || N == 1024 || N == 1280)))
+      unsupported("out16_fm: RESID on LEAN_FOLD_FM, N 512 .. 1280");
+    if (p->out_fm && !(fm && kind == WCB_PROJ_LN_GELU && (N == 2048 || N == 3072 || N == 4096 || N == 5120)))
+      unsupported("out_fm: LN_GELU on LEAN_FOLD_FM, N 2048 .. 5120");
+    if (p->a_fm && !fm) unsupported("a_fm: path LEAN_FOLD_FM");
+    if (fm && ln) REQUIRE(p->a_fm, "LEAN_FOLD_FM: the fragment-major rows (a_fm)");
+    if (tfold && ln) REQUIRE(p->rst_in, "RING_FOLD / WIDE: the 32-column statistics (rst_in)");
+    if (kind == WCB_PROJ_RESID && !p->a_fm) REQUIRE(p->a16, "RESID: a16");
+
+    // ---- derived operands (wcb_finalize_weights' preparation code)
+    const DType dt = DType(p->dtype);
+    const size_t e = esize(p->dtype);
+    hipStream_t st = (hipStream_t)stream;
+    struct Scratch { DevBuf b; ~Scratch() { b.release(); } } wg, wgfm, wfm, ub, cb, x16b, dh, wkf, wkt, wktfm;
+    auto fmcopy = [&](Scratch& s, const void* W, int n, int k) -> void* {
+      int nw = 0, kpw = 0;
+      if (dt == kF32 || !W || n % 16 || !lean_cfg(k, nw, kpw)) return nullptr;
+      s.b.ensure((size_t)n * k * e);
+      frag_major(dt, W, n, k, nw, kpw, s.b.p, st);
+      return s.b.p;
+    };
+    const void* x16 = p->a16;
+    if (ln && dt != kF32 && !x16 && !fm) {   // x16 = T(x)
+      x16b.b.ensure((size_t)M * K * e);
+      RepackArgs r;
+      r.dst = x16b.b.p; r.src = p->x; r.n[2] = M * K; r.s[2] = 1; r.t[2] = 1;
+      repack(dt, r, st);
+      x16 = x16b.b.p;
+    }
+    const bool need_fold = ln && dt != kF32 && (fold || tfold || p->u_out || p->c_out || p->wg_out);
+    if (need_fold) {   // W' = W·diag(γ), c, then u of the rounded W'
+      wg.b.ensure((size_t)N * K * e); ub.b.ensure((size_t)N * 4); cb.b.ensure((size_t)N * 4);
+      scale_cols(dt, p->W, N, K, p->ln_w, wg.b.p, st);
+      ln_fold(dt, p->W, N, K, p->ln_w, p->ln_b, p->bias, ub.b.as<float>(), cb.b.as<float>(), st);
+      ln_fold(dt, wg.b.p, N, K, nullptr, nullptr, nullptr, ub.b.as<float>(), nullptr, st);
+      if (fold || path == WCB_PATH_WIDE) fmcopy(wgfm, wg.b.p, N, K);
+    }
+    const int d = K, Hq = K / 64;
+    if (kq) {   // W_k,hᵀ: [H][d][64], element (h, c, i) = W_k[h·64 + i][c]
+      wkf.b.ensure((size_t)d * d * 4); wkt.b.ensure((size_t)d * d * e);
+      WeightView v;
+      v.shape[3] = (long)d * d; v.stride[3] = 1;
+      view_to_f32(dt, p->Wk, v, wkf.b.as<float>(), st);
+      RepackArgs r;
+      r.dst = wkt.b.p; r.src = wkf.b.as<float>();
+      r.n[0] = Hq; r.n[1] = d; r.n[2] = 64;
+      r.s[0] = 64L * d; r.s[1] = 1; r.s[2] = d;
+      r.t[0] = (long)d * 64; r.t[1] = 64; r.t[2] = 1;
+      repack(dt, r, st);
+      if (lean) fmcopy(wktfm, wkt.b.p, Hq * d, 64);
+    }
+
+    // ---- the launch's arguments: decode_rows()' block for the kind
+    GemmArgs g;
+    if (kind == WCB_PROJ_KQ) {
+      g = drow(p->a16, d, wkt.b.p, M, Hq * d, 64, p->out, (long)Hq * d);
+      g.a_grp_n = d; g.a_grp_off = 64; g.W_fm = wktfm.b.p;
+    } else if (kind == WCB_PROJ_RESID) {
+      g = drow(p->a_fm ? p->a_fm : p->a16, K, p->W, M, N, K, p->x, N);
+      g.bias = p->bias; g.resid = p->x; g.out_f32 = 1; g.st_out = p->st_out; g.st_nb = N / 16; g.out16 = p->out16;
+      if (lean || path == WCB_PATH_WIDE) g.W_fm = fmcopy(wfm, p->W, N, K);
+      g.a_fm = p->a_fm != nullptr;
+      g.out16_fm = p->out16_fm;
+    } else {
+      const int ldc = kind == WCB_PROJ_QKV ? p->n_split : N;
+      g = drow(p->x, K, p->W, M, N, K, kind == WCB_PROJ_XQK ? nullptr : p->out, ldc);
+      g.ln_w = p->ln_w; g.ln_b = p->ln_b; g.st_in = p->st_in; g.st_nb = K / 16;
+      g.ln_a16 = dt != kF32 ? x16 : nullptr;
+      g.bias = p->bias;
+      g.ln_u = ub.b.as<float>(); g.ln_c = cb.b.as<float>(); g.ln_wg = wg.b.p; g.ln_wg_fm = wgfm.b.p;
+      if (lean) g.W_fm = fmcopy(wfm, p->W, N, K);
+      if (kind == WCB_PROJ_QKV) {
+        g.mode = 2; g.n_split = p->n_split; g.kv_out = p->kv; g.hs_B = p->kv_B; g.hs_H = H; g.kv_T = p->kv_T;
+        g.pos = p->pos; g.kv_rps = rps;
+      }
+      if (kind == WCB_PROJ_LN_GELU) { g.act = 1; g.c_fm = p->out_fm; }
+      if (fm) { g.ln_a16 = p->a_fm; g.a_fm = 1; }
+      if (kind == WCB_PROJ_XQK) { g.xqk_wk = wktfm.b.p; g.xqk_out = p->out; g.hs_H = Hq; g.xqk_nch = p->xqk_nch; }
+    }
+    // ---- decode_rows()' proj(): > 64 rows on the tiles, else the lean switches
+    if (tiled) {
+      if (ln && tfold) {   // LayerNorm folded into the tile
+        g.A = x16; g.lda = K; g.W = g.ln_wg; g.ldw = K; g.W_fm = g.ln_wg_fm;
+        g.bias = g.ln_c; g.ln_w = g.ln_b = nullptr; g.st_in = nullptr; g.ln_a16 = nullptr;
+        g.rst_in = p->rst_in; g.rst_nb = K / 32;
+      } else if (ln) {     // a LayerNorm launch of its own
+        g.W_fm = nullptr; g.ln_u = nullptr;
+        dh.b.ensure((size_t)M * K * e);
+        layernorm(dt, p->x, g.ln_w, g.ln_b, dh.b.p, M, K, st);
+        g.A = dh.b.p; g.lda = K;
+        g.ln_w = g.ln_b = nullptr; g.st_in = nullptr; g.ln_a16 = nullptr;
+      }
+      g.tile = 2; g.skinny = 0; g.ring_kt = p->ring_kt == 2 ? 2 : 1;
+      if (kind == WCB_PROJ_RESID && tfold) g.rst_out = p->rst_out;
+      g.a_fm = 0; g.c_fm = 0; g.out16_fm = nullptr;
+      if (path == WCB_PATH_WIDE) {
+        if (!g.W_fm) unsupported("wide tiles: no fragment-major weights for this shape");
+        g.wide = kind == WCB_PROJ_LN_GELU ? 22 : 12;
+      } else {
+        g.W_fm = nullptr;
+      }
+    } else {
+      if (!ln || !(fold || tfold)) { g.ln_u = nullptr; g.ln_c = nullptr; g.ln_wg = nullptr; g.ln_wg_fm = nullptr; }
+      g.lean = lean;
+      g.lean_fold = fold && g.ln_w && g.ln_wg_fm && g.ln_u && g.ln_c;
+      if (fold && ln && !g.lean_fold) unsupported("folded lean launch: no folded operands for this shape");
+    }
+    int taken = kTakenNone;
+    g.taken = &taken;
+    try {
+      gemm(dt, g, st);
+    } catch (const WcbError&) {
+      throw;
+    } catch (const std::runtime_error& err) {   // an operand combination no launcher of the path takes
+      throw WcbError(WCB_ERR_UNSUPPORTED, err.what());
+    }
+    HIPCHK(hipGetLastError());
+    if (need_fold) {
+      if (p->u_out) HIPCHK(hipMemcpyAsync(p->u_out, ub.b.p, (size_t)N * 4, hipMemcpyDeviceToDevice, st));
+      if (p->c_out) HIPCHK(hipMemcpyAsync(p->c_out, cb.b.p, (size_t)N * 4, hipMemcpyDeviceToDevice, st));
+      if (p->wg_out) HIPCHK(hipMemcpyAsync(p->wg_out, wg.b.p, (size_t)N * K * e, hipMemcpyDeviceToDevice, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));   // the derived operands are freed on return
+    if (p->taken) *p->taken = taken;
+    const int want = kind == WCB_PROJ_XQK ? kTakenXqk : lean ? kTakenLean : path == WCB_PATH_DEC ? kTakenDecMf :
+                     path == WCB_PATH_WIDE ? kTakenWide : kTakenRingDec;
+    if ((taken & 255) != want)
+      throw WcbError(WCB_ERR_UNSUPPORTED, "the path's launcher does not cover this launch (launcher " + std::to_string(taken & 255) +
+                                              " ran; the outputs are not the path's)");
+  });
+}
+
 // wcb_op_lm_head_lse, and wcb_op_lm_head_sample (seeds non-null: the sampled kernels, step on the device)
 static int op_lm_head(int dtype, const void* A, const void* W, int M, int V, int K, int walkers, float* logits, long ld,
                       float* lse, int32_t* argmax, void* stream, bool sampled, float temperature, const uint64_t* seeds,
