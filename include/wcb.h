@@ -393,6 +393,35 @@ int wcb_op_lm_head_rules(int dtype, const void* A, const void* W, int M, int V, 
                          const wcb_token_rules* rules, int eos, const int32_t* generated, int gen_ld,
                          const int32_t* lens, float* logits, long ld, int32_t* next_ids, void* stream);
 
+/* ---- repeat rules of the greedy decoder: HF's repetition_penalty and no_repeat_ngram_size, applied on the chip at
+ * every step (RepetitionPenaltyLogitsProcessor, NoRepeatNGramLogitsProcessor; semantics: csrc/reprule.h, DESIGN.md
+ * §5i). hist = what HF's processors see as input_ids for the row: its live prompt tokens, the start token, the
+ * forced language / task tail (a detected language included) and every token generated so far; the dead left-padding
+ * slots of a ragged batch are not part of it. On the raw f32 logits, before the boost, the EOS mask and the deny lists:
+ *   repetition_penalty p > 0:  x[v] = x[v] < 0 ? x[v]·p : x[v] / p  for every distinct v in hist (f32: one multiply or
+ *                              one correctly rounded division)
+ *   no_repeat_ngram_size n:    with L = len(hist) >= n >= 1, x[hist[i+n-1]] = -inf for every i in [0, L-n] whose n-1
+ *                              tokens from hist[i] equal the last n-1 tokens of hist
+ * p = 1 and n = 0 mean off. Token log-probs are unaffected (raw log-softmax). */
+typedef struct { float repetition_penalty; int no_repeat_ngram_size; } wcb_repeat_rules;
+/* Handle state, like wcb_set_token_rules: applies to every greedy decode begun afterwards (wcb_generate, _biased,
+ * _scored, _prompted, _lang, wcb_decode_begin* / wcb_decode_step); NULL removes the rules. No device work: every decode
+ * writes the two values into its own context on its stream, so decodes with different values replay one captured
+ * graph. WCB_ERR_STATE before wcb_finalize_weights or while a step-wise decode is open; WCB_ERR_ARG for a penalty that
+ * is not finite or <= 0, or n < 0. With the rules installed, refused at decode time with WCB_ERR_UNSUPPORTED:
+ * num_beams > 1, a sampled decode, token rules with timestamps = 1, wcb_generate_windows, and a model with more than
+ * 448 text positions or more than 53248 vocabulary entries (the history and the banned set of a row live in LDS). */
+int wcb_set_repeat_rules(wcb_handle*, const wcb_repeat_rules* /* NULL: none */);
+/* HOST, no GPU: both rules applied in place to scores[vocab] of a row whose history is hist[0..n_hist) — the same
+ * inline functions the kernels compile. WCB_ERR_ARG for an id outside [0, vocab). */
+int wcb_repeat_rules_apply_host(const wcb_repeat_rules*, int vocab, const int32_t* hist, int n_hist, float* scores);
+/* The LM head with the per-row seen bitmap plus the history pass of the finalize on caller operands (as
+ * wcb_op_lm_head_rules; lam = 0, no EOS mask): row m's history is hist[m·hist_ld .. + lens[m]) (HOST, 1 <= lens[m] <=
+ * min(hist_ld, 448)); the bitmap is built from it by the decode-start kernel; next_ids[M] int32 DEVICE, logits f32. */
+int wcb_op_lm_head_repeat(int dtype, const void* A, const void* W, int M, int V, int K, int walkers,
+                          const wcb_repeat_rules* rules, int eos, const int32_t* hist, int hist_ld,
+                          const int32_t* lens, float* logits, long ld, int32_t* next_ids, void* stream);
+
 /* ---- token-level timestamps from cross-attention (HF return_token_timestamps / _extract_token_timestamps, per
  * clip and batch-invariant; semantics: csrc/dtw.h). A teacher-forced post-pass over the ids any
  * decode produced: the causal prefill of wcb_forward_enc with the LM head off and a capture kernel after the cross

@@ -52,6 +52,10 @@ def token_rules(suppress=(), begin_suppress=(), timestamps=False, timestamp_begi
     return r, (sup, beg)
 
 
+class WcbRepeatRules(C.Structure):
+    _fields_ = [("repetition_penalty", C.c_float), ("no_repeat_ngram_size", C.c_int)]
+
+
 class WcbAlignCfg(C.Structure):
     _fields_ = [("heads", C.POINTER(C.c_int32)), ("n_heads", C.c_int), ("median_width", C.c_int),
                 ("num_frames", C.POINTER(C.c_int32))]
@@ -183,6 +187,10 @@ SIGNATURES = {
     "wcb_token_rules_apply_host": (C.c_int, [C.POINTER(WcbTokenRules), C.c_int, C.c_int, _P, C.c_int, _P]),
     "wcb_op_lm_head_rules": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(WcbTokenRules),
                                        C.c_int, _P, C.c_int, _P, _P, C.c_long, _P, _P]),
+    "wcb_set_repeat_rules": (C.c_int, [_P, C.POINTER(WcbRepeatRules)]),
+    "wcb_repeat_rules_apply_host": (C.c_int, [C.POINTER(WcbRepeatRules), C.c_int, _P, C.c_int, _P]),
+    "wcb_op_lm_head_repeat": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(WcbRepeatRules),
+                                        C.c_int, _P, C.c_int, _P, _P, C.c_long, _P, _P]),
     "wcb_align": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, _P, C.c_int, C.POINTER(WcbAlignCfg), _P, _P, _P]),
     "wcb_op_align_capture": (C.c_int, [C.c_int, _P, C.c_long, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, _P]),

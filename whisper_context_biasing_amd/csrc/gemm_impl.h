@@ -1065,6 +1065,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(GemmArgs g) {
   const bool mask_eos = g.sel_val && *g.sel_step < g.sel_min_new;
   // token rules (wave-uniform, null: none): the deny bitmap of this step
   const uint32_t* deny = !g.sel_val ? nullptr : (g.sel_deny0 && *g.sel_step == 0) ? g.sel_deny0 : g.sel_deny;
+  const uint32_t* seen = g.sel_val ? g.sel_seen : nullptr;   // repeat rules (wave-uniform, null: none)
   [[maybe_unused]] int smp_step = 0;
   [[maybe_unused]] float smp_inv_t = 1.f;
   if constexpr (SAMPLE) { smp_step = *g.sel_step; smp_inv_t = *g.sel_inv_t; }
@@ -1119,6 +1120,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(GemmArgs g) {
         if constexpr (SAMPLE) x = sample_perturb(x, smp_inv_t, sample_noise(g.sel_seeds[row], smp_step, nn));
         if (mask_eos && nn == g.sel_eos) x = -INFINITY;
         if (deny && deny_bit(deny, nn)) x = -INFINITY;
+        if (seen && deny_bit(seen + (long)row * g.sel_seen_w, nn)) x = -INFINITY;
         xi = nn;
       }
 #pragma unroll
@@ -1346,9 +1348,16 @@ __global__ __launch_bounds__(NW * 64) void gemm_dec_kernel(GemmArgs g) {
   // token rules (wave-uniform, null: none): this step's deny bitmap, the tile's word fetched like the root bits
   const uint32_t* deny = !g.sel_val ? nullptr : (g.sel_deny0 && *g.sel_step == 0) ? g.sel_deny0 : g.sel_deny;
   uint32_t dnw = deny ? deny[(ct * 16) >> 5] : 0u, dnn = 0u;
+  // repeat rules (wave-uniform, null: none): the seen bitmap is per row, so every epilogue output reads the word of
+  // its own row for the tile — issued at the head of the tile, consumed after the MFMAs and the LDS exchange
+  const uint32_t* seen = g.sel_val ? g.sel_seen : nullptr;
   int buf = 0;
   for (; ct < ntile; ct += gridDim.x) {
     const int n0 = ct * 16;
+    uint32_t snw[EP];
+#pragma unroll
+    for (int it = 0; it < EP; ++it)
+      snw[it] = seen ? seen[(long)min(mb + ((it * NT + tid) >> 4), g.M - 1) * g.sel_seen_w + (n0 >> 5)] : 0u;
     // P (persistent column walk): the tile PD - 1 walker steps ahead goes in flight behind this one
     // (clamped: an unconditional load keeps hipcc from draining the queue at the loop head); the next
     // tile's boost bits one step ahead
@@ -1428,7 +1437,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_dec_kernel(GemmArgs g) {
             x = bias_bonus(x, g.sel_lam, pf_rb[it] + (int)((rbw >> (nn & 31)) & 1u));
           if constexpr (SAMPLE) x = sample_perturb(x, smp_inv_t, sample_noise(pf_seed[it], smp_step, nn));
           if (mask_eos && nn == g.sel_eos) x = -INFINITY;
-          if ((dnw >> (nn & 31)) & 1u) x = -INFINITY;   // (no rules: the word is 0)
+          if (((dnw | snw[it]) >> (nn & 31)) & 1u) x = -INFINITY;   // (no rules: the words are 0)
           xi = nn;
         }
 #pragma unroll
@@ -2502,6 +2511,8 @@ static void gemm_t(const GemmArgs& g, hipStream_t s) {
     throw std::runtime_error("internal error: sampling on a launch that is not the greedy LM head");
   if ((g.sel_deny || g.sel_deny0) && (!g.sel_val || g.tile || g.M > 64))
     throw std::runtime_error("internal error: token rules on a launch that is not the greedy LM head");
+  if (g.sel_seen && (!g.sel_val || g.tile || g.M > 64 || g.sel_seen_w <= 0))
+    throw std::runtime_error("internal error: repeat rules on a launch that is not the greedy LM head");
   auto took = [&](int v) { if (g.taken) *g.taken = v; };   // host side only: which launcher ran
   took(kTakenNone);
   if (g.tile) {   // decoder rows > 64 (beams, prefill): MFMA tiles, each weight tile read once per 64-128 rows

@@ -36,7 +36,24 @@
 // lane-strided-then-butterfly order, and takes the best timestamp when logsumexp(timestamps) > max(text)
 // (rule 5: both sides carry the same log-softmax normaliser) or when it is the better candidate outright. A row
 // whose every candidate is -inf emits EOS. The log-prob of the chosen token stays raw logit − logsumexp(raw).
+//
+// Repeat rules (REP instantiations, SelectArgs::rep; reprule.h): with hist = the row's live prompt slots and its
+// generated tokens, x[v] is penalised (x < 0 ? x·p : x / p) for every v in hist and set to -inf for every v that
+// would complete an n-gram of hist, before the boost. Both rules touch only tokens of hist, so one bit per (row,
+// token) — the seen bitmap, set from the prompt at decode start and by every finalize for its chosen token —
+// splits the work: the vocabulary pass treats a seen token as a denied one, and the finalize walks the history
+// (at most n_text_ctx positions, one wave) scoring each position's token from the logits with the penalty, the ban
+// and the exact n(s, v) (trans(s), then the root bit / the clip's root children). Exact for any p > 0:
+//   1. an unseen token is exact in the partials: neither rule touches it, and the trans(s) / root-children
+//      re-scoring of the unseen ones is the argument above, unchanged;
+//   2. every seen token is offered once per occurrence with its exact score — the occurrences of one token carry
+//      the same value under the same index (the banned set is collected first, so a ban through any occurrence
+//      reaches all of them), and the re-scoring loops skip seen tokens, so no inexact copy of one competes;
+//   3. no ordering between seen and unseen scores is assumed: with p < 1 a seen token may rise above the unseen
+//      best, and it wins the merge then; the argmax over the union, lowest index on ties, is better()'s.
+// The chosen token's log-prob stays raw. Not combined with SAMPLE or the timestamp grammar (refused by the runtime).
 #include <algorithm>
+#include <stdexcept>
 
 #include "common.h"
 #include "kernels.h"
@@ -70,6 +87,7 @@ __global__ __launch_bounds__(256) void select_partial_kernel(SelectArgs a) {
   [[maybe_unused]] const int step = SAMPLE ? *a.step : 0;
   [[maybe_unused]] const float inv_t = SAMPLE ? *a.inv_t : 1.f;
   [[maybe_unused]] const uint64_t seed = SAMPLE ? a.seeds[m] : 0ull;
+  const uint32_t* seen = a.rep.seen ? a.rep.seen + (long)m * a.rep.words : nullptr;   // repeat rules (null: none)
   float bv = -INFINITY;
   int bi = 0x7fffffff;
   for (int v = v0 + threadIdx.x; v < v1; v += 256) {
@@ -78,6 +96,7 @@ __global__ __launch_bounds__(256) void select_partial_kernel(SelectArgs a) {
     if constexpr (SAMPLE) x = sample_perturb(x, inv_t, sample_noise(seed, step, v));
     if (mask_eos && v == a.eos) x = -INFINITY;
     if (deny && deny_bit(deny, v)) x = -INFINITY;
+    if (seen && deny_bit(seen, v)) x = -INFINITY;
     if (better(x, v, bv, bi)) { bv = x; bi = v; }
   }
 #pragma unroll
@@ -105,10 +124,13 @@ __global__ __launch_bounds__(256) void select_partial_kernel(SelectArgs a) {
 // EMB: the row's next-step input embedding in the same launch (k_norm.hip embed_kernel's arithmetic and
 // stats grouping, 64 columns per pass).
 // RAG (ragged prompts, with EMB): the row's next position is the next slot minus the row's prompt offset.
-template <typename T, bool EMB, bool FOREST, bool SAMPLE = false, bool RAG = false>
+// REP (repeat rules, never with SAMPLE): the history pass of the comment at the top; every line of it sits under
+// `if constexpr (REP)`, so the other instantiations are the code they were.
+template <typename T, bool EMB, bool FOREST, bool SAMPLE = false, bool RAG = false, bool REP = false>
 __global__ __launch_bounds__(64) void select_finalize_kernel(SelectArgs a) {
   const int m = blockIdx.x, lane = threadIdx.x;
   const int step = *a.step;
+  [[maybe_unused]] const uint32_t* seen = REP ? a.rep.seen + (long)m * a.rep.words : nullptr;
   const int pos0 = EMB ? *a.pos : 0;   // read before this row's ticket: the last arriver advances it
   const bool mask_eos = step < a.min_new;
   float bv = -INFINITY;
@@ -159,6 +181,9 @@ __global__ __launch_bounds__(64) void select_finalize_kernel(SelectArgs a) {
       if constexpr (SAMPLE) x = sample_perturb(x, inv_t, sample_noise(seed, step, v));
       if (mask_eos && v == a.eos) x = -INFINITY;
       if ((deny && deny_bit(deny, v)) || v < text_lo) x = -INFINITY;
+      if constexpr (REP) {   // a seen token is the history pass's to offer
+        if (deny_bit(seen, v)) x = -INFINITY;
+      }
       if (better(x, v, bv, bi)) { bv = x; bi = v; }
     }
     if constexpr (FOREST) {   // the clip's root children: n = k - d + 1 (the vocabulary pass gave them k - d)
@@ -168,8 +193,70 @@ __global__ __launch_bounds__(64) void select_finalize_kernel(SelectArgs a) {
         if constexpr (SAMPLE) x = sample_perturb(x, inv_t, sample_noise(seed, step, v));
         if (mask_eos && v == a.eos) x = -INFINITY;
         if ((deny && deny_bit(deny, v)) || v < text_lo) x = -INFINITY;
+        if constexpr (REP) {
+          if (deny_bit(seen, v)) x = -INFINITY;
+        }
         if (better(x, v, bv, bi)) { bv = x; bi = v; }
       }
+    }
+  }
+  if constexpr (REP) {
+    // the row's history into LDS: its live prompt slots, then what it has generated. The host keeps L within
+    // kRepMaxHist (check_repeat refuses n_text_ctx > kRepMaxHist, and every decode has P + max_new <= n_text_ctx + 1,
+    // so L <= P + max_new - 1 <= n_text_ctx): the clamp below only guards the LDS arrays, it never drops a token
+    __shared__ int hs[kRepMaxHist];
+    __shared__ uint32_t banw[kRepBanWords];   // the banned tokens of this step, one bit per token (words <= kRepBanWords)
+    const float p = __int_as_float(a.rep.par[0]);
+    const int n = a.rep.par[1];
+    const int off = a.rep.poff ? a.rep.poff[m] : 0;
+    const int Lp = a.rep.P - off;
+    const int L = min(Lp + step, kRepMaxHist);
+    for (int i = lane; i < L; i += 64)
+      hs[i] = i >= Lp ? a.out_ids[(long)m * a.out_ld + i - Lp]
+                      : a.rep.prompt ? a.rep.prompt[(long)m * a.rep.prompt_ld + off + i] : a.rep.start_tok;
+    const bool ngram = n >= 1 && L >= n;
+    if (ngram)
+      for (int i = lane; i < a.rep.words; i += 64) banw[i] = 0u;
+    __syncthreads();
+    // pass 1: the banned set — the token after every history position that matches the suffix. A bit per token, so
+    // a ban through any occurrence reaches every occurrence, and pass 2 asks one bit per position
+    if (ngram) {
+      for (int i = lane; i <= L - n; i += 64) {
+        const int v = hs[i + n - 1];
+        if (v >= 0 && v < a.V && rep_ngram_match(hs, L, n, i)) atomicOr(&banw[v >> 5], 1u << (v & 31));
+      }
+    }
+    __syncthreads();
+    // pass 2: every history position offers its token with the exact score
+    const float* row = a.logits + (long)m * a.ld;
+    const int d = a.st_depth[s], k = a.st_keep[s];
+    for (int j = lane; j < L; j += 64) {
+      const int v = hs[j];
+      if (v < 0 || v >= a.V) continue;
+      float x = rep_penalty(row[v], p);
+      if (ngram && ((banw[v >> 5] >> (v & 31)) & 1u)) x = -INFINITY;
+      if (a.lam != 0.f) {   // n(s, v): trans(s), then the root bit / the clip's root children, else k - d
+        int nu = k - d;
+        bool listed = false;
+        for (int t = t0; t < t1 && !listed; ++t)
+          if (a.trans_tok[t] == v) {
+            const int d2 = a.st_depth[a.trans_dst[t]];
+            nu = d2 - d + min(k, d + 1 - d2);
+            listed = true;
+          }
+        if (!listed) {
+          if constexpr (FOREST) {
+            for (int t = a.forest.rc_off[m]; t < a.forest.rc_off[m + 1]; ++t)
+              if (a.forest.rc_tok[t] == v) nu = k - d + 1;
+          } else {
+            nu += (int)((a.root_bits[v >> 5] >> (v & 31)) & 1u);
+          }
+        }
+        x = bias_bonus(x, a.lam, nu);
+      }
+      if (mask_eos && v == a.eos) x = -INFINITY;
+      if (deny && deny_bit(deny, v)) x = -INFINITY;
+      if (better(x, v, bv, bi)) { bv = x; bi = v; }
     }
   }
 #pragma unroll
@@ -200,7 +287,7 @@ __global__ __launch_bounds__(64) void select_finalize_kernel(SelectArgs a) {
     const float lse_ts = tsum > 0.f ? tm + logf(tsum) : -INFINITY;
     if (lse_ts > bv || better(tv, ti, bv, bi)) { bv = tv; bi = ti; }
   }
-  if ((deny || ts_on) && !(bv > -INFINITY)) bi = 0x7fffffff;   // every candidate excluded: EOS (below)
+  if ((REP || deny || ts_on) && !(bv > -INFINITY)) bi = 0x7fffffff;   // every candidate excluded: EOS (below)
   const bool fin = a.finished[m] != 0;
   // a row with no comparable value (all NaN) keeps bi = INT_MAX: emit EOS rather than an index past
   // the vocabulary (the next step's embedding lookup must stay in bounds)
@@ -268,6 +355,9 @@ __global__ __launch_bounds__(64) void select_finalize_kernel(SelectArgs a) {
     a.state[m] = dst;
     a.rowbase[m] = a.st_keep[dst] - a.st_depth[dst];
     a.next_ids[m] = tok;
+    if constexpr (REP) {   // the chosen token joins the history (this row's words: no other wave writes them)
+      if (tok >= 0 && tok < a.V) a.rep.seen[(long)m * a.rep.words + (tok >> 5)] |= 1u << (tok & 31);
+    }
     if (ts_on && !fin) {   // finished rows keep their state
       ts_advance(a.ts, tok, w0, w1);
       a.ts_state[2 * m] = w0;
@@ -345,24 +435,28 @@ void write_i32(int* dst, const int* host_src, int n, hipStream_t s) {
   }
 }
 
-template <bool FOREST, bool SAMPLE>
+template <bool FOREST, bool SAMPLE, bool REP = false>
 static void select_finalize_launch(const SelectArgs& a, hipStream_t s) {
   if (a.emb && a.pos_off) {   // ragged prompts: the embedding at the row's own position
-    if (a.dtype == kBF16) WCB_LAUNCH((select_finalize_kernel<bf16_t, true, FOREST, SAMPLE, true>), dim3(a.M), dim3(64), 0, s, a);
-    else if (a.dtype == kF16) WCB_LAUNCH((select_finalize_kernel<f16_t, true, FOREST, SAMPLE, true>), dim3(a.M), dim3(64), 0, s, a);
-    else WCB_LAUNCH((select_finalize_kernel<float, true, FOREST, SAMPLE, true>), dim3(a.M), dim3(64), 0, s, a);
+    if (a.dtype == kBF16) WCB_LAUNCH((select_finalize_kernel<bf16_t, true, FOREST, SAMPLE, true, REP>), dim3(a.M), dim3(64), 0, s, a);
+    else if (a.dtype == kF16) WCB_LAUNCH((select_finalize_kernel<f16_t, true, FOREST, SAMPLE, true, REP>), dim3(a.M), dim3(64), 0, s, a);
+    else WCB_LAUNCH((select_finalize_kernel<float, true, FOREST, SAMPLE, true, REP>), dim3(a.M), dim3(64), 0, s, a);
   } else if (!a.emb) {
-    WCB_LAUNCH((select_finalize_kernel<float, false, FOREST, SAMPLE>), dim3(a.M), dim3(64), 0, s, a);
+    WCB_LAUNCH((select_finalize_kernel<float, false, FOREST, SAMPLE, false, REP>), dim3(a.M), dim3(64), 0, s, a);
   } else if (a.dtype == kBF16) {
-    WCB_LAUNCH((select_finalize_kernel<bf16_t, true, FOREST, SAMPLE>), dim3(a.M), dim3(64), 0, s, a);
+    WCB_LAUNCH((select_finalize_kernel<bf16_t, true, FOREST, SAMPLE, false, REP>), dim3(a.M), dim3(64), 0, s, a);
   } else if (a.dtype == kF16) {
-    WCB_LAUNCH((select_finalize_kernel<f16_t, true, FOREST, SAMPLE>), dim3(a.M), dim3(64), 0, s, a);
+    WCB_LAUNCH((select_finalize_kernel<f16_t, true, FOREST, SAMPLE, false, REP>), dim3(a.M), dim3(64), 0, s, a);
   } else {
-    WCB_LAUNCH((select_finalize_kernel<float, true, FOREST, SAMPLE>), dim3(a.M), dim3(64), 0, s, a);
+    WCB_LAUNCH((select_finalize_kernel<float, true, FOREST, SAMPLE, false, REP>), dim3(a.M), dim3(64), 0, s, a);
   }
 }
 void select_finalize(const SelectArgs& a, hipStream_t s) {
-  if (a.seeds) {   // temperature sampling: the sampled instantiations
+  if (a.rep.seen) {   // repeat rules: the REP instantiations (greedy, no timestamp grammar)
+    if (a.seeds || a.ts.on) throw std::runtime_error("internal error: repeat rules with sampling or the timestamp grammar");
+    if (a.forest.root) select_finalize_launch<true, false, true>(a, s);
+    else select_finalize_launch<false, false, true>(a, s);
+  } else if (a.seeds) {   // temperature sampling: the sampled instantiations
     if (a.forest.root) select_finalize_launch<true, true>(a, s);
     else select_finalize_launch<false, true>(a, s);
   } else if (a.forest.root) {
@@ -370,6 +464,23 @@ void select_finalize(const SelectArgs& a, hipStream_t s) {
   } else {
     select_finalize_launch<false, false>(a, s);
   }
+}
+
+// decode start with repeat rules: one workgroup per row clears the row's words, then sets the bits of its live
+// prompt slots (ids outside [0, V) ignored)
+__global__ __launch_bounds__(256) void rep_init_kernel(RepArgs r, int V) {
+  const int m = blockIdx.x;
+  uint32_t* w = r.seen + (long)m * r.words;
+  for (int i = threadIdx.x; i < r.words; i += 256) w[i] = 0u;
+  __syncthreads();
+  const int off = r.poff ? r.poff[m] : 0;
+  for (int i = off + threadIdx.x; i < r.P; i += 256) {
+    const int v = r.prompt ? r.prompt[(long)m * r.prompt_ld + i] : r.start_tok;
+    if (v >= 0 && v < V) atomicOr(&w[v >> 5], 1u << (v & 31));
+  }
+}
+void rep_init(const RepArgs& r, int rows, int V, hipStream_t s) {
+  WCB_LAUNCH(rep_init_kernel, dim3(rows), dim3(256), 0, s, r, V);
 }
 
 // decode start with per-utterance lists: every row in its clip's root state (the zero fill means "state 0",

@@ -4,6 +4,7 @@
 #include <hip/hip_ext.h>
 #include <stdint.h>
 
+#include "reprule.h"
 #include "tsrule.h"
 
 namespace wcb {
@@ -142,6 +143,10 @@ struct GemmArgs {
   // partials still take the raw value). sel_deny0, when non-null, replaces sel_deny at step 0 (*sel_step == 0).
   // A run-time, wave-uniform null check: no instantiation of its own
   const uint32_t* sel_deny = nullptr; const uint32_t* sel_deny0 = nullptr;
+  // LM head, repeat rules (nullable, with sel_val; reprule.h): the per-row seen bitmap, row m's sel_seen_w words at
+  // sel_seen + m·sel_seen_w — a set bit makes the column's argmax candidate -inf exactly as a denied one, so the
+  // partials hold the best UNSEEN token (the finalize offers the seen ones itself). Wave-uniform null check
+  const uint32_t* sel_seen = nullptr; int sel_seen_w = 0;
   // HOST pointer (nullable, never read on the device): the launcher gemm() took for this call, a GemmTaken value
   // (+ 256·detail for the ring tiles: 1 = 64x64, 2 = 64x32, 3 = 32x32). The kernel-level entry points report it;
   // the runtime leaves it null
@@ -276,6 +281,22 @@ struct ForestArgs {
 // state[r] = root[r / nb], rowbase[r] = 0 (rowbase nullable) for the R decoder rows of a decode start
 void forest_init(const ForestArgs& f, int* state, int* rowbase, int R, int nb, hipStream_t s);
 
+// Repeat rules of a greedy decode (reprule.h; k_select.hip). seen: one bit per (row, token) of the row's history,
+// row m's `words` 32-bit words at seen + m·words. par: two DEVICE words, the bits of the f32 penalty and the n-gram
+// size — values, so a captured graph holds for every (p, n). The history of row m is its live prompt slots
+// prompt[m·prompt_ld + poff[m] .. m·prompt_ld + P) (prompt null: the start token alone, P = 1; poff null: 0) followed
+// by the row's generated tokens (SelectArgs::out_ids). seen null: off
+constexpr int kRepMaxHist = 448;   // max_target_positions of every Whisper size: the history a finalize holds in LDS
+constexpr int kRepBanWords = 1664; // 53248 / 32: the widest bitmap (RepArgs::words) whose banned set a finalize holds in LDS
+struct RepArgs {
+  uint32_t* seen = nullptr; int words = 0;
+  const int* par = nullptr;
+  const int* prompt = nullptr; long prompt_ld = 0; int P = 1; int start_tok = 0;
+  const int* poff = nullptr;
+};
+// decode start: every row's bitmap cleared, then the bits of its live prompt slots set (ids outside [0, V) ignored)
+void rep_init(const RepArgs& r, int rows, int V, hipStream_t s);
+
 // greedy selection with bias-list boost (see csrc/k_select.hip for the semantics)
 struct SelectArgs {
   const float* logits = nullptr; long ld = 0; int M = 0; int V = 0;
@@ -324,6 +345,8 @@ struct SelectArgs {
   // no-speech probability (out_nsp non-null; needs out_logprob, whose merged logsumexp it reuses): at
   // step 0 out_nsp[m] = exp(logits[m][nsp_token] − lse) over the raw logits; later steps leave it alone
   float* out_nsp = nullptr; int nsp_token = 0;
+  // repeat rules (rep.seen non-null: the REP instantiations; never with seeds or ts.on — refused by the runtime)
+  RepArgs rep;
 };
 void select_greedy(const SelectArgs& a, hipStream_t s);          // vocabulary pass + finalize
 void select_finalize(const SelectArgs& a, hipStream_t s);        // partials already written (fused LM head)

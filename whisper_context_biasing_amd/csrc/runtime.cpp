@@ -154,6 +154,7 @@ struct wcb_state {
   bool sampling = false; // wcb_decode_enable_sampling: every step draws its tokens (the context's samp words)
   bool ragged = false;   // per-clip prompts of different lengths (left-padded to P): every step reads the context's poff
   bool no_speech = false; // wcb_decode_enable_no_speech: the first step also writes the context's nsp floats
+  RepArgs rep;           // repeat rules of this decode (the handle's at its start; seen null: none)
 };
 
 // lean decode projection classes stamped inside the replayed decode graph (stamps pass), by region
@@ -206,9 +207,9 @@ struct DecCtx {
   // the captured decode steps, one slot per kind of call: a ruled (wcb_set_token_rules), a sampled and a scored
   // (token log-probs) decode each launch other kernels or arguments, so every combination replays its own graphs
   // and no kind of call evicts another's
-  StepGraphs graphs[16];
-  StepGraphs& graphs_of(bool ruled, bool sampled, bool scored, bool no_speech = false) {
-    return graphs[8 * no_speech + 4 * ruled + 2 * sampled + scored];
+  StepGraphs graphs[32];
+  StepGraphs& graphs_of(bool ruled, bool sampled, bool scored, bool no_speech = false, bool repeat = false) {
+    return graphs[16 * repeat + 8 * no_speech + 4 * ruled + 2 * sampled + scored];
   }
   void drop_graphs() {
     for (StepGraphs& g : graphs) g.drop();
@@ -227,6 +228,11 @@ struct DecCtx {
   // graph key only the fact); the left-padded prompts and the offsets go up on the decode stream from the pinned
   // p_stage, as the forest does
   DevBuf poff;
+  // repeat rules (wcb_set_repeat_rules): seen = the per-row token bitmap [kRepRows][vocab_pad / 32],
+  // rep_par = two words (the bits of the f32 penalty, the n-gram size). Both allocated once by the first such decode
+  // and never moved: the graphs hold the addresses, the graph key only the fact — the values are written by value on
+  // the decode stream at the start of every such decode, as samp is
+  DevBuf seen, rep_par;
   // no-speech probability (wcb_generate_windows, wcb_decode_enable_no_speech): one float per row [64], written by
   // the scored finalize at step 0; allocated once and never moved (the graphs of such decodes hold its address)
   DevBuf nsp;
@@ -388,6 +394,10 @@ struct wcb_handle {
   bool rules_on = false, rules_has0 = false;
   TsRule rules_ts;
   DevBuf rules_deny, rules_deny0;
+  // repeat rules (wcb_set_repeat_rules): the two values; the device state lives in the decode contexts
+  bool rep_on = false;
+  float rep_p = 1.f;
+  int rep_n = 0;
   // encoder GEMM tile order (option "enc_raster"): bands of n row panels with the column tiles outer
   // (GemmArgs::raster; 0 = row-major). 8 measured best with the round-3 ring kernel (whisper-small:
   // QKV 185 -> 177, fc1 297 -> 281, out 118 -> 116 us, fc2 within noise; profiles/r03f_enc_gemm_bench.txt)
@@ -731,6 +741,8 @@ void wcb_destroy(wcb_handle* h) {
     if (D.done_h) (void)hipHostFree(D.done_h);
     D.forest.release();
     D.poff.release();
+    D.seen.release();
+    D.rep_par.release();
     D.nsp.release();
     D.lang.release();
     if (D.p_stage) (void)hipHostFree(D.p_stage);
@@ -1479,6 +1491,9 @@ struct StepCfg {
   // greedy select with token log-probs: the first step also writes every row's no-speech probability here (the
   // context's nsp). Null: the step as it always was
   float* nsp_out = nullptr;
+  // greedy select, repeat rules (start_repeat; seen null: the step as it always was): the LM head reads the seen
+  // bitmap, the finalize is the REP instantiation
+  RepArgs rep;
 };
 
 // the capture of one teacher-forced pass of wcb_align: per layer the selected (head, slot in the list) pairs; the
@@ -1837,6 +1852,7 @@ void decode_rows(wcb_handle* h, const StepCfg& c, int b0, int nb, int chain, hip
         lm.sel_seeds = c.samp + 1 + b0;
       }
       lm.sel_deny = c.deny; lm.sel_deny0 = c.deny0;   // token rules (null: none)
+      if (c.rep.seen) { lm.sel_seen = c.rep.seen + (size_t)b0 * c.rep.words; lm.sel_seen_w = c.rep.words; }   // repeat rules
     }
     if (lm_tiled) {
       proj("lm_head", lm);
@@ -1910,6 +1926,7 @@ void decode_step(wcb_handle* h, const StepCfg& c) {
     }
     if (c.samp) { s.inv_t = reinterpret_cast<const float*>(c.samp); s.seeds = c.samp + 1; }
     s.deny = c.deny; s.deny0 = c.deny0; s.ts = c.ts; s.ts_state = ri.ts_state;
+    s.rep = c.rep;
     if (c.nsp_out && c.logprob_out) { s.out_nsp = c.nsp_out; s.nsp_token = h->d.vocab - kTimestampTokens - 2; }
     if (c.embedded) {   // the next step's input embedding in the same launch (embed()'s outputs)
       const bool r32 = h->dec_gemm && lnf_possible(h);
@@ -2102,6 +2119,42 @@ const uint64_t* install_sampling(DecCtx& D, float temperature, const uint64_t* s
   std::memcpy(w + 2, seeds, (size_t)rows * 8);
   write_i32(D.samp.as<int>(), w, 2 + 2 * rows, D.hs);
   return D.samp.as<uint64_t>();
+}
+
+// Repeat rules of a greedy decode in context D, after its prompt rows are final (a detected language
+// patched in) and before its first step: the two values into the context's words by value on the decode stream
+// (write_i32, as install_sampling), every row's seen bitmap cleared and set from its live prompt slots. The prompt is
+// what decode_start left in D.forced — one shared row (stride 0), [rows][P], left-padded with the offsets in D.poff —
+// or the start token alone. Returns the device view the steps of this decode carry.
+constexpr int kRepRows = 64;
+void check_repeat(const wcb_handle* h, int nb, bool sampled, bool windows) {
+  if (!h->rep_on) return;
+  if (nb > 1)
+    throw WcbError(WCB_ERR_UNSUPPORTED, "repeat rules are greedy only (num_beams = 1; wcb_set_repeat_rules(h, NULL) removes them)");
+  if (sampled) throw WcbError(WCB_ERR_UNSUPPORTED, "repeat rules with sampling are not supported (greedy only)");
+  if (h->rules_on && h->rules_ts.on)
+    throw WcbError(WCB_ERR_UNSUPPORTED, "repeat rules with timestamp decoding are not supported (token rules with timestamps = 1)");
+  if (windows) throw WcbError(WCB_ERR_UNSUPPORTED, "repeat rules with wcb_generate_windows are not supported");
+  if (h->d.n_text_ctx > kRepMaxHist)
+    throw WcbError(WCB_ERR_UNSUPPORTED, "repeat rules: more than 448 text positions");
+  if (h->vocab_pad / 32 > kRepBanWords)
+    throw WcbError(WCB_ERR_UNSUPPORTED, "repeat rules: a vocabulary above 53248 tokens");
+}
+RepArgs start_repeat(wcb_handle* h, DecCtx& D, int rows, int P, bool has_prefix, int prompt_ld, bool ragged) {
+  REQUIRE(rows >= 1 && rows <= kRepRows, "repeat rules: 1 .. 64 rows");
+  const int words = h->vocab_pad / 32;
+  D.seen.ensure((size_t)kRepRows * words * 4);   // once: vocab_pad is fixed by the weights
+  D.rep_par.ensure(8);
+  int w[2] = {0, h->rep_n};
+  std::memcpy(w, &h->rep_p, 4);
+  write_i32(D.rep_par.as<int>(), w, 2, D.hs);
+  RepArgs r;
+  r.seen = D.seen.as<uint32_t>(); r.words = words; r.par = D.rep_par.as<int>();
+  r.prompt = has_prefix ? D.forced.as<int>() : nullptr; r.prompt_ld = prompt_ld; r.P = has_prefix ? P : 1;
+  r.start_tok = h->d.decoder_start_token_id;
+  r.poff = ragged ? D.poff.as<int>() : nullptr;
+  rep_init(r, rows, h->d.vocab, D.hs);
+  return r;
 }
 
 // Lt: the total length cap (prefix + max new tokens, MaxLength), Tc: cache positions, Lg: max new tokens
@@ -2397,6 +2450,7 @@ static void generate_impl(wcb_handle* h, const GenCall& c) {
       throw WcbError(WCB_ERR_UNSUPPORTED, "token rules are greedy only (num_beams = 1; wcb_set_token_rules(h, NULL) removes them)");
     if (h->rules_on && h->rules_ts.on && smp)
       throw WcbError(WCB_ERR_UNSUPPORTED, "timestamp decoding with sampling is not supported (greedy only)");
+    check_repeat(h, nb, smp != nullptr, c.win != nullptr);
     if (nb > 1 && c.out_logprobs)
       throw WcbError(WCB_ERR_UNSUPPORTED, "token log-probs are greedy only (beam search: out_seq_scores)");
     if (nb == 1 && c.out_seq_scores)
@@ -2482,6 +2536,8 @@ static void generate_impl(wcb_handle* h, const GenCall& c) {
       detect_pass(h, sc, c.lang->lang_begin, c.lang->n_lang, c.lang->candidates, c.lang->out_ids, c.lang->out_probs, P,
                   P - 1 - c.lang->column_from_end);
     decode_prompt(h, sc, P, c.prefix != nullptr || prompted);
+    const bool has_prefix = c.prefix != nullptr || prompted;
+    if (h->rep_on) sc.rep = st.rep = start_repeat(h, D, R, P, has_prefix, sc.forced_ld, st.ragged);
     sc.lm_head = true;
     sc.select = true;
     sc.embedded = nb == 1;   // greedy: decode_prompt embedded the first step's input
@@ -2495,7 +2551,9 @@ static void generate_impl(wcb_handle* h, const GenCall& c) {
     if (ruled)   // what a ruled graph bakes in beside the bitmaps' stable addresses
       kn += snprintf(key + kn, sizeof key - kn, "/R%d.%d.%d.%d", sc.ts.on, sc.ts.ts0, sc.ts.max_init, (int)h->rules_has0);
     if (st.ragged)   // ragged prompts: the windowed kernels reading the context's offsets — the fact, never the lengths
-      snprintf(key + kn, sizeof key - kn, "/G");
+      kn += snprintf(key + kn, sizeof key - kn, "/G");
+    if (sc.rep.seen)   // repeat rules: the fact and how the history reads the prompt rows — never p or n
+      snprintf(key + kn, sizeof key - kn, "/Q%d", !has_prefix ? 0 : sc.forced_ld ? 2 : 1);
     // per-launch HIP events (profiling bit 0) cannot bracket nodes of a replayed graph: eager launches
     const bool use_graph = cfg->use_graph && !h->prof;
     // The decode step replays as a hipGraph; steps_per_graph steps are captured into one graph so the
@@ -2504,7 +2562,7 @@ static void generate_impl(wcb_handle* h, const GenCall& c) {
     // string (never the seeds or the temperature), so no kind of call evicts another's.
     const int chunk = h->steps_per_graph;
     int done = 0, steps = 0;
-    StepGraphs& g = D.graphs_of(ruled, smp != nullptr, c.out_logprobs != nullptr, c.out_no_speech != nullptr);
+    StepGraphs& g = D.graphs_of(ruled, smp != nullptr, c.out_logprobs != nullptr, c.out_no_speech != nullptr, sc.rep.seen != nullptr);
     if (use_graph && (!g.one || g.key != key)) capture_steps(h, sc, g, key);
     // Natural-EOS mode (reference decoding) polls the device "all finished" step one chunk behind:
     // chunk k+1 is queued before the host waits for chunk k's flag, so the GPU never idles on the
@@ -2668,6 +2726,7 @@ static void decode_begin(wcb_handle* h, const void* enc, int B, int nb, const in
   REQUIRE(nb <= kMaxBeams, "num_beams must be in [2, 8] (greedy: num_beams = 1)");
   if (nb > 1 && h->rules_on)
     throw WcbError(WCB_ERR_UNSUPPORTED, "token rules are greedy only (num_beams = 1; wcb_set_token_rules(h, NULL) removes them)");
+  check_repeat(h, nb, false, false);
   const int R = B * nb;
   REQUIRE(R <= 64 * DecCtx::kMaxSub, "batch x num_beams > 512 rows: split the batch");
   REQUIRE(h->nctx < wcb_handle::kMaxCtx, "step-wise decoding needs a free decode context (decode_contexts <= 3)");
@@ -2693,6 +2752,7 @@ static void decode_begin(wcb_handle* h, const void* enc, int B, int nb, const in
   const StepCfg sc = decode_start(h, ci, *st, prefix, /*shared=*/false, h->empty_bias.get(), plen);
   if (lang) detect_pass(h, sc, lang->lang_begin, lang->n_lang, lang->candidates, lang->out_ids, lang->out_probs, P, P - 1 - lang->column_from_end);
   decode_prompt(h, sc, P, prefix != nullptr);
+  if (h->rep_on) st->rep = start_repeat(h, D, R, P, prefix != nullptr, sc.forced_ld, st->ragged);
   HIPCHK(hipStreamSynchronize(D.hs));
   h->step_state = st.release();
   *out = h->step_state;
@@ -2802,6 +2862,7 @@ int wcb_decode_step(wcb_handle* h, wcb_state* st, const wcb_bias* bias, int32_t*
       if (st->sampling) sc.samp = D.samp.as<uint64_t>();
       if (st->ragged) sc.pos_off = D.poff.as<int>();
       apply_rules(h, sc);   // (fixed for the whole decode: wcb_set_token_rules is refused while the state is open)
+      sc.rep = st->rep;
     }
     if (st->forest) sc.forest = &st->fd;
     decode_step(h, sc);
@@ -2926,6 +2987,7 @@ int wcb_decode_enable_sampling(wcb_handle* h, wcb_state* st, float temperature, 
     if (st->nb > 1) throw WcbError(WCB_ERR_UNSUPPORTED, "sampling is greedy only (a beam-search state)");
     if (h->rules_on && h->rules_ts.on)
       throw WcbError(WCB_ERR_UNSUPPORTED, "timestamp decoding with sampling is not supported (greedy only)");
+    if (st->rep.seen) throw WcbError(WCB_ERR_UNSUPPORTED, "repeat rules with sampling are not supported (greedy only)");
     if (st->fwd != 0) throw WcbError(WCB_ERR_STATE, "wcb_decode_enable_sampling on a forward cache (wcb_forward_cached state)");
     if (st->steps != 0) throw WcbError(WCB_ERR_STATE, "wcb_decode_enable_sampling: after the first step (right after wcb_decode_begin)");
     install_sampling(D, temperature, seeds, st->B);
@@ -4101,6 +4163,136 @@ int wcb_op_lm_head_rules(int dtype, const void* A, const void* W, int M, int V, 
     select_finalize(s, st);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st));   // the scratch buffers and the pageable host sources live until here
+  });
+}
+
+// ---- repeat rules (csrc/reprule.h)
+extern "C++" {
+namespace {
+void check_repeat_rules(const wcb_repeat_rules* r) {
+  REQUIRE(std::isfinite(r->repetition_penalty) && r->repetition_penalty > 0.f, "repetition_penalty must be finite and > 0");
+  REQUIRE(r->no_repeat_ngram_size >= 0, "no_repeat_ngram_size must be >= 0");
+}
+}  // namespace
+}  // extern "C++"
+
+int wcb_set_repeat_rules(wcb_handle* h, const wcb_repeat_rules* r) {
+  return guarded(h, [&] {
+    REQUIRE(h, "null handle");
+    if (!h->ready) throw WcbError(WCB_ERR_STATE, "weights not finalized");
+    if (h->step_state) throw WcbError(WCB_ERR_STATE, "wcb_set_repeat_rules: a step-wise decode is active (wcb_decode_end first)");
+    if (!r) { h->rep_on = false; return; }
+    check_repeat_rules(r);
+    // (no device work: every decode writes the values into its own context, stream-ordered, at its start)
+    h->rep_p = r->repetition_penalty;
+    h->rep_n = r->no_repeat_ngram_size;
+    h->rep_on = !(h->rep_p == 1.f && h->rep_n == 0);   // both at "off": the decode as it always was
+  });
+}
+
+int wcb_repeat_rules_apply_host(const wcb_repeat_rules* r, int vocab, const int32_t* hist, int n_hist, float* scores) {
+  return guarded(nullptr, [&] {
+    REQUIRE(r && scores && vocab > 0 && n_hist >= 0 && (n_hist == 0 || hist), "bad argument");
+    check_repeat_rules(r);
+    for (int i = 0; i < n_hist; ++i) REQUIRE(hist[i] >= 0 && hist[i] < vocab, "history id outside [0, vocab)");
+    const float p = r->repetition_penalty;
+    const int n = r->no_repeat_ngram_size, L = n_hist;
+    std::vector<char> seen((size_t)vocab, 0);
+    for (int i = 0; i < L; ++i) {   // every distinct token once
+      if (seen[hist[i]]) continue;
+      seen[hist[i]] = 1;
+      scores[hist[i]] = rep_penalty(scores[hist[i]], p);
+    }
+    if (n >= 1 && L >= n)
+      for (int i = 0; i <= L - n; ++i)
+        if (rep_ngram_match(hist, L, n, i)) scores[hist[i + n - 1]] = -INFINITY;
+  });
+}
+
+int wcb_op_lm_head_repeat(int dtype, const void* A, const void* W, int M, int V, int K, int walkers,
+                          const wcb_repeat_rules* rules, int eos, const int32_t* hist, int hist_ld, const int32_t* lens,
+                          float* logits, long ld, int32_t* next_ids, void* stream) {
+  return guarded(nullptr, [&] {
+    REQUIRE(A && W && logits && next_ids && rules && hist && lens && M > 0 && M <= 64 && V > 0 && K > 0 && ld >= V && eos >= 0 &&
+                eos < V && hist_ld >= 1,
+            "bad argument (1 <= M <= 64, ld >= V, 0 <= eos < V, every pointer)");
+    REQUIRE(dtype >= WCB_BF16 && dtype <= WCB_F32, "dtype");
+    REQUIRE(walkers >= 0 && walkers <= 4096, "walkers: 0 (default) .. 4096");
+    check_repeat_rules(rules);
+    if (V > kRepBanWords * 32) throw WcbError(WCB_ERR_UNSUPPORTED, "repeat rules: a vocabulary above 53248 tokens");
+    const DType dt = DType(dtype);
+    if (!gemm_dec_supported(dt, K) && K != 32 && K != 2560)
+      throw WcbError(WCB_ERR_UNSUPPORTED, "K: 64, 128, 256, 384, 512, 768, 1024, 1280 (column walk) or 32, 2560 (skinny kernel)");
+    // the histories as left-padded prompt rows [M][hist_ld] with their offsets: the layout of a ragged decode at step 0
+    std::vector<int> rows((size_t)M * hist_ld, 0), offs((size_t)M, 0);
+    for (int m = 0; m < M; ++m) {
+      REQUIRE(lens[m] >= 1 && lens[m] <= hist_ld && lens[m] <= kRepMaxHist, "lens outside [1, min(hist_ld, 448)]");
+      offs[m] = hist_ld - lens[m];
+      for (int i = 0; i < lens[m]; ++i) {
+        const int tok = hist[(size_t)m * hist_ld + i];
+        REQUIRE(tok >= 0 && tok < V, "history id outside [0, vocab)");
+        rows[(size_t)m * hist_ld + offs[m] + i] = tok;
+      }
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const int wk = walkers > 0 ? walkers : kDecWalkers;
+    const int nchunk = lm_head_partials(dt, K, V, wk);
+    struct Scratch { DevBuf b; ~Scratch() { b.release(); } } pv, pi, zi, bm, hb, wpad, wfm;
+    const size_t np = (size_t)M * nchunk * 4, words = ((size_t)V + 127) / 128 * 4;
+    pv.b.ensure(np); pi.b.ensure(np);
+    bm.b.ensure((size_t)M * words * 4);
+    hb.b.ensure(((size_t)M * hist_ld + M + 2) * 4);
+    int* d_rows = hb.b.as<int>();
+    int* d_offs = d_rows + (size_t)M * hist_ld;
+    int* d_par = d_offs + M;
+    write_i32(d_rows, rows.data(), M * hist_ld, st);
+    write_i32(d_offs, offs.data(), M, st);
+    int par[2] = {0, rules->no_repeat_ngram_size};
+    std::memcpy(par, &rules->repetition_penalty, 4);
+    write_i32(d_par, par, 2, st);
+    RepArgs rp;
+    rp.seen = bm.b.as<uint32_t>(); rp.words = (int)words; rp.par = d_par;
+    rp.prompt = d_rows; rp.prompt_ld = hist_ld; rp.P = hist_ld; rp.start_tok = 0; rp.poff = d_offs;
+    rep_init(rp, M, V, st);
+    // one zeroed int block: the counters (step 0), then the per-row arrays of a one-step decode with an empty forest
+    const size_t zn = 16 + (size_t)10 * M + 8;
+    zi.b.ensure(zn * 4);
+    int* z = zi.b.as<int>();
+    int* zstate = z + 16;
+    int* zts = z + 16 + 6 * M + 8;
+    int* zout = zts + 2 * M;
+    GemmArgs lm = drow(A, K, W, M, V, K, logits, ld);
+    lm.out_f32 = 1;
+    lm.walkers = wk;
+    lm.sel_val = pv.b.as<float>(); lm.sel_idx = pi.b.as<int>();
+    lm.sel_step = z;   // min_new 0: no EOS mask; lam 0: no boost
+    lm.sel_seen = rp.seen; lm.sel_seen_w = rp.words;
+    int nw = 0, kpw = 0;
+    if (dt != kF32 && gemm_dec_supported(dt, K) && lean_cfg(K, nw, kpw)) {   // as op_lm_head: fragment-major weights
+      const size_t e = esize(dtype), vp = (size_t)(V + 15) / 16 * 16;
+      wpad.b.ensure(vp * K * e);
+      wfm.b.ensure(vp * K * e);
+      HIPCHK(hipMemcpyAsync(wpad.b.p, W, (size_t)V * K * e, hipMemcpyDeviceToDevice, st));
+      frag_major(dt, wpad.b.p, (int)vp, K, nw, kpw, wfm.b.p, st);
+      lm.W_fm = wfm.b.p;
+    }
+    gemm(dt, lm, st);
+    SelectArgs s;
+    s.logits = logits; s.ld = ld; s.M = M; s.V = V;
+    s.trans_off = zstate + 5 * M + 2; s.trans_tok = nullptr; s.trans_dst = nullptr;
+    s.st_depth = zstate + 5 * M + 4; s.st_keep = zstate + 5 * M + 5;
+    s.state = zstate; s.finished = zstate + M; s.rowbase = zstate + 2 * M;
+    s.forest.root = zstate + 3 * M; s.forest.rc_off = zstate + 4 * M;   // [M + 1] zeros
+    s.eos = eos; s.pad = eos; s.min_new = 0;
+    s.step = z; s.pos = z + 1; s.all_done = z + 2;
+    s.ticket_unfin = reinterpret_cast<unsigned long long*>(z + 4);
+    s.next_ids = next_ids; s.out_ids = zout; s.out_ld = 2;
+    s.part_val = lm.sel_val; s.part_idx = lm.sel_idx; s.nchunk = nchunk;
+    s.ts_state = zts;
+    s.rep = rp;
+    select_finalize(s, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));   // the scratch buffers live until here
   });
 }
 

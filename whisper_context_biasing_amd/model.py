@@ -369,6 +369,7 @@ class WhisperCB:
         self._bias_retired: List[BiasList] = []
         self._word_start: Optional[np.ndarray] = None
         self._rules_key = None   # the token rules installed on the handle (wcb_set_token_rules), None: none
+        self._repeat_key = None  # the repeat rules (p, n) installed on the handle (wcb_set_repeat_rules), None: none
         self._loaded = False
         self._cache: Optional["DecoderCache"] = None   # the open forward(use_cache=True) state, if any
         # options last: a rejected option raises with every attribute __del__ reads already set
@@ -559,7 +560,13 @@ class WhisperCB:
 
     # ---------------------------------------------------------------------------- generation
     def _install_rules(self, key) -> None:
-        """Make `key` the handle's token rules (handle state, like a generation config; a no-op when it already is)."""
+        """Make `key` the handle's token rules (handle state, like a generation config; a no-op when it already is);
+        a key that carries repeat rules (request.split_rules) installs or removes those the same way."""
+        key, repeat = _request.split_rules(key)
+        if repeat != self._repeat_key:
+            r = None if repeat is None else C.byref(_lib.WcbRepeatRules(*repeat))
+            _lib.check(self._lib.wcb_set_repeat_rules(self._h, r), self._h, "wcb_set_repeat_rules")
+            self._repeat_key = repeat
         if key == self._rules_key:
             return
         if key is None:
@@ -585,7 +592,8 @@ class WhisperCB:
                  compression_ratio_threshold: Optional[float] = 2.4, return_timestamps: bool = False,
                  suppress_tokens=None, begin_suppress_tokens=None, max_initial_timestamp: Optional[float] = None,
                  return_token_timestamps: bool = False, alignment_heads=None, num_frames=None,
-                 median_filter_width: int = 7, language=None, task: Optional[str] = None, language_candidates=None, **kwargs):
+                 median_filter_width: int = 7, language=None, task: Optional[str] = None, language_candidates=None,
+                 repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None, **kwargs):
         """Greedy (num_beams = 1, the reference's eval setting) or HF beam
         search (num_beams = 2..8, [tf] generation/utils.py:3208) on the device.
 
@@ -672,6 +680,16 @@ class WhisperCB:
         exactly the call without them. ValueError: any of them on an English-only model, `task` without `language`,
         `language_candidates` without "auto", an unknown language (or one this vocabulary has no token for), a list
         whose length is not B, differing languages or "auto" with `num_beams > 1` or `return_token_timestamps`.
+
+        `repetition_penalty` / `no_repeat_ngram_size` (HF's; None = the generation config's value when it has one, else
+        1.0 / 0 = off): applied on the device at every greedy step to the raw logits, before the boost and
+        every other rule (wcb_set_repeat_rules). The history they look at is the clip's own prompt, the start token, the
+        forced language / task tail (a detected language included) and the tokens generated so far — not the padding of
+        a ragged batch, so a clip decodes as it decodes alone. Token log-probs stay raw. They work with bias lists,
+        `prompt_ids`, `language=`, `output_logprobs`, the deny lists, `min_new_tokens`, `block=False`, `use_graph` both
+        ways and above 64 clips; two calls that differ only in the two values replay the same graphs. ValueError with
+        `num_beams > 1`, `temperature > 0` or a temperature sequence, and `return_timestamps=True` (hence
+        `transcribe_long`). With both off the call is exactly the call without them.
         """
         if not self._loaded:
             raise _lib.WcbError("weights not loaded")
@@ -687,7 +705,8 @@ class WhisperCB:
             suppress_tokens=suppress_tokens, begin_suppress_tokens=begin_suppress_tokens,
             max_initial_timestamp=max_initial_timestamp, return_token_timestamps=return_token_timestamps,
             alignment_heads=alignment_heads, num_frames=num_frames, median_filter_width=median_filter_width,
-            language=language, task=task, language_candidates=language_candidates)
+            language=language, task=task, language_candidates=language_candidates,
+            repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size)
         x = self._features(x)
         res = self._generate_with_fallback(x, req) if req.temperatures is not None else self._decode(x, req)
         if req.align is not None:   # right after the decode: one library call leaves its encoder state to the alignment
@@ -1032,7 +1051,8 @@ class WhisperCB:
                      bias_lists=None, logprobs: bool = False, temperature: float = 0.0, seed=0,
                      return_timestamps: bool = False, suppress_tokens=None, begin_suppress_tokens=None,
                      max_initial_timestamp: Optional[float] = None, no_speech: bool = False, language=None,
-                     task: Optional[str] = None, language_candidates=None) -> "StepDecoder":
+                     task: Optional[str] = None, language_candidates=None, repetition_penalty: Optional[float] = None,
+                     no_repeat_ngram_size: Optional[int] = None) -> "StepDecoder":
         """Step-wise decoding from an encoder output [B, 1500, d] (this model's dtype, on its device): the
         streaming form of generate() (wcb_decode_begin / wcb_decode_begin_beams). Greedy (num_beams = 1) or
         beam search (num_beams 2..8; `max_length` = generate()'s, the beams' length cap: None = the
@@ -1050,8 +1070,14 @@ class WhisperCB:
         not with sampling: ValueError). `no_speech=True` (needs `logprobs=True`: ValueError): StepDecoder.no_speech_prob()
         gives every clip's no-speech probability after the first step. `language` / `task` / `language_candidates`:
         generate()'s (the forced tail after the start token; "auto" detects on the device before the prefill —
-        wcb_decode_begin_lang); the StepDecoder then has `languages` [B] int64 and, with "auto", `language_probs`."""
+        wcb_decode_begin_lang); the StepDecoder then has `languages` [B] int64 and, with "auto", `language_probs`.
+        `repetition_penalty` / `no_repeat_ngram_size`: generate()'s repeat rules for every step of this decode (greedy
+        only, not with sampling or timestamps: ValueError)."""
         T, nb = _request.sampling_temperature(temperature), int(num_beams)
+        repeat = _request.repeat_key(repetition_penalty, no_repeat_ngram_size, self.generation_config)
+        if repeat is not None and (nb != 1 or T > 0.0 or return_timestamps):
+            raise ValueError("repetition_penalty / no_repeat_ngram_size are greedy only: not with num_beams > 1, sampling "
+                             "or return_timestamps")
         if no_speech and not logprobs:
             raise ValueError("no_speech needs logprobs=True (it reuses the log-probs' logsumexp)")
         rules = _request.rules_key(self.dims, return_timestamps, suppress_tokens, begin_suppress_tokens, max_initial_timestamp)
@@ -1110,7 +1136,7 @@ class WhisperCB:
         shared, bias_lists = _request.bias_source(B, bias_list, bias_lists, bias_boost)
         bl = self._automaton(shared, bias_boost)
         st = C.c_void_p()
-        self._install_rules(rules)
+        self._install_rules(rules if repeat is None else (rules or _request.NO_TOKEN_RULES) + (repeat,))
         flat = (pre.ctypes.data, pre.shape[1]) if pre is not None else (None, 1)
         lang_ids = lang_probs = keep_lang = None
         if packed is not None and plan is not None and plan.auto:

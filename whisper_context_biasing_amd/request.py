@@ -104,6 +104,34 @@ def rules_key(dims, return_timestamps=False, suppress_tokens=None, begin_suppres
     return (sup, beg, ts, mi)
 
 
+NO_TOKEN_RULES = ((), (), False, -1)   # rules_key()'s form of "no deny list, no grammar" when only repeat rules ride along
+
+
+def repeat_key(repetition_penalty=None, no_repeat_ngram_size=None, generation_config=None):
+    """The repeat rules `repetition_penalty` / `no_repeat_ngram_size` ask for (HF's arguments; None: the
+    generation config's when it has one, else 1.0 / 0) as (p, n), or None when both are off (p == 1.0 and n == 0)."""
+    p, n = repetition_penalty, no_repeat_ngram_size
+    if p is None:
+        p = getattr(generation_config, "repetition_penalty", None)
+    if n is None:
+        n = getattr(generation_config, "no_repeat_ngram_size", None)
+    p, n = 1.0 if p is None else p, 0 if n is None else n
+    if isinstance(p, bool) or not isinstance(p, (int, float, np.integer, np.floating)) or not (math.isfinite(float(p)) and float(p) > 0):
+        raise ValueError(f"`repetition_penalty` has to be a strictly positive float, but is {p!r}")
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or int(n) < 0:
+        raise ValueError(f"`no_repeat_ngram_size` has to be a non-negative integer, but is {n!r}")
+    p, n = float(np.float32(p)), int(n)   # the library takes an f32
+    return None if p == 1.0 and n == 0 else (p, n)
+
+
+def split_rules(rules):
+    """A request's `rules` value -> (the token rules as rules_key() gives them, or None; the repeat rules (p, n), or None)."""
+    if rules is None or len(rules) == 4:
+        return rules, None
+    token = tuple(rules[:4])
+    return (None if token == NO_TOKEN_RULES else token), rules[4]
+
+
 def align_args(dims, B: int, alignment_heads, num_frames, median_filter_width) -> dict:
     """The checked alignment arguments (ValueError for what wcb_align refuses)."""
     W = int(median_filter_width)
@@ -254,7 +282,7 @@ class DecodeRequest:
     per_clip_prompts: bool = False
     bias_shared: Any = None                       # phrases, or a prebuilt automaton
     bias_lists: Optional[List[List[List[int]]]] = None
-    rules: Optional[tuple] = None                 # rules_key()
+    rules: Optional[tuple] = None                 # rules_key(), + ((p, n),) with repeat rules on (split_rules)
     scored: bool = False
     as_dict: bool = False
     timestamps: bool = False
@@ -321,7 +349,8 @@ def resolve(dims, generation_config, B: int, *, bias_spans=None, max_length=None
             bias_lists=None, per_utterance_bias=False, output_logprobs=False, temperature=0.0, seed=0, do_sample=None,
             logprob_threshold=-1.0, compression_ratio_threshold=2.4, return_timestamps=False, suppress_tokens=None,
             begin_suppress_tokens=None, max_initial_timestamp=None, return_token_timestamps=False, alignment_heads=None,
-            num_frames=None, median_filter_width=7, language=None, task=None, language_candidates=None) -> DecodeRequest:
+            num_frames=None, median_filter_width=7, language=None, task=None, language_candidates=None,
+            repetition_penalty=None, no_repeat_ngram_size=None) -> DecodeRequest:
     """generate()'s arguments for a batch of B clips -> the DecodeRequest, or the ValueError of what the call cannot mean.
     `generation_config` is the effective one (it defaults max_length and num_beams); `bias_spans` as bias_source() takes it."""
     nb = int(num_beams if num_beams is not None else getattr(generation_config, "num_beams", 1) or 1)
@@ -332,6 +361,7 @@ def resolve(dims, generation_config, B: int, *, bias_spans=None, max_length=None
     temps = tuple(sampling_temperature(t) for t in temperature) if fallback else None   # do_sample plays no part then
     T = 0.0 if fallback else sampling_temperature(temperature, do_sample)
     rules = rules_key(dims, return_timestamps, suppress_tokens, begin_suppress_tokens, max_initial_timestamp)
+    repeat = repeat_key(repetition_penalty, no_repeat_ngram_size, generation_config)
     lang = resolve_language(dims, B, language, task, language_candidates, timestamps=bool(return_timestamps), num_beams=nb,
                             token_timestamps=bool(return_token_timestamps))
     for refused, why in (   # what the library, or the host side of the decode, cannot do
@@ -341,6 +371,11 @@ def resolve(dims, generation_config, B: int, *, bias_spans=None, max_length=None
             (per_clip and len(prompt or ()) != B, f"prompt_ids holds {len(prompt or ())} prompts, the batch {B} clips"),
             (return_token_timestamps and not block,
              "return_token_timestamps reads the ids of the finished decode: block=False is not supported"),
+            (repeat is not None and nb != 1, "repetition_penalty / no_repeat_ngram_size are greedy only: num_beams must be 1"),
+            (repeat is not None and (fallback or T > 0.0),
+             "repetition_penalty / no_repeat_ngram_size with sampling or a temperature fallback are not supported"),
+            (repeat is not None and bool(return_timestamps),
+             "repetition_penalty / no_repeat_ngram_size with return_timestamps are not supported (hence not in transcribe_long)"),
             (rules is not None and nb != 1,
              "suppress_tokens / begin_suppress_tokens / return_timestamps are greedy only: num_beams must be 1"),
             (return_timestamps and (fallback or T > 0.0),
@@ -354,6 +389,8 @@ def resolve(dims, generation_config, B: int, *, bias_spans=None, max_length=None
         if refused:
             raise ValueError(why)
     shared, lists = bias_source(B, bias_list, bias_lists, bias_boost, bias_spans, per_utterance_bias)
+    if repeat is not None:   # carried inside `rules`: the token rules' 4-tuple (or its empty form), then (p, n)
+        rules = (rules or NO_TOKEN_RULES) + (repeat,)
     req = DecodeRequest(
         B=B, num_beams=nb, max_length=int(max_length), min_new_tokens=int(min_new_tokens), bias_boost=float(bias_boost),
         use_graph=bool(use_graph), block=bool(block), temperature=T,
